@@ -6,26 +6,31 @@ A "step" is one stereo pair through the hot path (cost volume -> CBCA -> SGM -> 
 LR check -> interpolation -> sub-pixel -> median -> range-gated Gaussian) with the inputs
 (normalised images + features or raw volumes) already resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config kitti_fast|kitti_slow|mb_slow]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config kitti_fast|kitti_slow|mb_slow] [--dump-outputs DIR] [--full]
 
 Default workload at N = 1: BASELINE.json configs[1], KITTI 2012 fast, 370x1226, disp_max 228 (the configuration the
-reference's own timing is quoted on); the 1000x1500x256 accurate configuration the north-star target is quoted on rides in
-the same line as `north_star` (specified texture + two realistic pairs), KITTI accurate as `kitti_accurate`.
+reference's own timing is quoted on); with --full the 1000x1500x256 accurate configuration the north-star target is quoted on
+rides in the same line as `north_star` (specified texture + two realistic pairs), KITTI accurate as `kitti_accurate`.
 Default workload at N > 1: BASELINE.json configs[4] -- one Middlebury-size accurate pair per GPU, every rank its own seeded
 pair (images 1234 + rank, raw volumes 7 + rank).  One rank per GPU (launched by torch.distributed.run, or spawned by this
 script itself when WORLD_SIZE is not set), weak scaling, no data-path collective; the finished disparity maps are gathered
 with one RCCL all-gather per step on a side stream, so that step k + 1's mc_predict overlaps step k's gather.
 
-The timed region is EXACTLY --steps steps between barrier + device synchronisation; it is repeated (whole blocks of --steps
-steps) until at least ~1 s has been timed, `ms_per_step` / `value` are the MEDIAN block, `ms_per_step_min` the best one.
+The timed region is EXACTLY --steps steps between barrier + device synchronisation.  With --min-seconds S > 0 it is repeated
+(whole blocks of --steps steps) until at least S s have been timed, `ms_per_step` / `value` are then the MEDIAN block,
+`ms_per_step_min` the best one.  --dump-outputs DIR writes what the last timed step computed (the disparity map; with N > 1
+also the gathered maps of all ranks) as DIR/<name>.npy, float32, so that two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0).  `value` = Mega-pixel-disparities / s = n_gpus * 2 volumes *
-H*W*D / 1e6 / seconds-per-step.  Beside the contract's fields the line carries
+H*W*D / 1e6 / seconds-per-step.  A plain run sets up, warms up, times the steps and prints the line.  With --full the line
+also carries (the --no-* options drop single records of a --full run)
+  stage_ms      per-stage HIP-event times of extra untimed steps
+  multi_gpu     (N > 1) the ranks that took part, the gathered maps checked, per-rank compute / gather times
   roofline      the kernel group with the largest MEASURED time among those with a byte model
                 (StereoJoin / CBCA / SGM), + `kernels`: all of them
   verify        the timed configuration's outputs bit-compared with main.lua's stereo_predict over
                 the REFERENCE'S OWN kernels (oracle/_ref) on the same GPU and inputs
-  north_star    (default run, N=1) the 1000x1500x256 accurate configuration: ms/pair, the per-volume
+  north_star    (default config, N=1) the 1000x1500x256 accurate configuration: ms/pair, the per-volume
                 SGM + cross-aggregation sweep against SURVEY 8(d)'s 47 V budget, and its own verify
   cpu_baseline  the oracle on the host cores (min of 3)
   ops_ms_per_pair  the unchanged-main.lua route: the same pair through the op-by-op adcensus.* calls
@@ -151,6 +156,27 @@ def same_bits_dev(a, b):
     na, nb = torch.isnan(a), torch.isnan(b)
     bad = (na != nb) | (~na & (a.view(torch.int32) != b.view(torch.int32)))
     return not bool(bad.any().item())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: the arrays a caller of the timed path received in its last step, one DIR/<name>.npy each, float32.
+    An array that would take the total past 64 MB is replaced by a fixed sample of its elements (seed 0, sorted flat indices,
+    saved beside it as <name>_index.npy)."""
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > left:
+            n = max(1, (left // 2) // 12)   # float32 value + int64 index per sampled element, half of what is left
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(n, a.size), replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx)
+            left -= idx.nbytes
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def verify_against_reference(cfg, xb, kw, prm, D, ws, cfg_key):
@@ -783,15 +809,23 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the CPU-baseline band (0 = auto)")
     ap.add_argument("--no-ref-gpu", action="store_true", help="skip the verify leg (reference's own kernels on this GPU)")
-    ap.add_argument("--no-north-star", action="store_true", help="skip the 1000x1500x256 and KITTI-accurate sub-records of the default run")
+    ap.add_argument("--no-north-star", action="store_true", help="skip the 1000x1500x256 and KITTI-accurate sub-records of a --full run")
     ap.add_argument("--no-ops", action="store_true", help="skip timing the op-by-op (unchanged main.lua) route")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the timed block of --steps steps until this much has been timed")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the timed block of --steps steps until this much has been timed (default 0: one block, exactly --steps steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the records that take runs of their own: stage times + roofline, verify, op-by-op route, "
+                         "CPU baseline, the sub-records of the default config, the multi-rank checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--dry-run", action="store_true", help="build this rank's inputs, print their fingerprint as JSON and exit (no GPU needed)")
     ap.add_argument("--pairs-in-flight", type=int, default=0,
                     help="K > 0: only the `pipelined` record of --config with 1..K pairs in flight (K streams, K workspaces), as one JSON line")
     ap.add_argument("--pair", choices=("sample", "natural", "texture", "mixed"), default=None,
                     help="image pair (default per config, PAIR_OF): real-scene arm statistics or the Gaussian texture")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config is None:
         args.config = "kitti_fast" if args.gpus <= 1 else "mb_slow"
 
@@ -902,9 +936,8 @@ def main():
 
     for k in range(args.warmup):
         step_and_gather(k)
-    # the timed region: EXACTLY --steps steps between barrier + synchronise on both sides, max over ranks; repeated as whole
-    # blocks until >= --min-seconds have been timed (20 KITTI-fast steps are 58 ms: clocks, first touches and box-to-box spread
-    # would all sit inside one blink), median block reported, best block beside it
+    # the timed region: EXACTLY --steps steps between barrier + synchronise on both sides, max over ranks; with --min-seconds
+    # repeated as whole blocks until that much has been timed, median block reported, best block beside it
     blocks = []
     while True:
         sync()
@@ -924,9 +957,17 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = world * 2.0 * H * W * D / 1e6 / (dt / args.steps)
 
-    # ---- multi-rank bookkeeping: who took part, and is the gathered batch what the ranks computed ----
+    if args.dump_outputs and rank == 0:
+        # one rank: every step writes `out`; several: the last timed step wrote map (steps - 1) % 2, and the sync above has
+        # waited for its all-gather on the side stream
+        dumped = dict(disp=out if world == 1 else outs[(args.steps - 1) & 1])
+        if world > 1:
+            dumped["disp_all_ranks"] = gathered
+        dump_outputs(args.dump_outputs, dumped)
+
+    # ---- multi-rank bookkeeping (--full): who took part, and is the gathered batch what the ranks computed ----
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         ids = torch.tensor([rank], dtype=torch.int64, device="cpu" if one_gpu else device)
         seen = [torch.zeros_like(ids) for _ in range(world)]
         dist.all_gather(seen, ids)
@@ -984,10 +1025,10 @@ def main():
                           "the all-gather of the (H,W) maps entered by all ranks together (here on the compute stream; in the timed "
                           "loop it runs on a side stream under the next step's mc_predict)" % nrep)
 
-    # live per-stage HIP-event timing (same stream) for the roofline
+    # live per-stage HIP-event timing (same stream) for the roofline (--full)
     roof = stage = None
     acc = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         reps = max(3, min(10, args.steps))
         if fc_ws is not None:  # the FC stack runs before mc_predict: time it with events on the same stream
             for _ in range(reps):
@@ -1014,7 +1055,7 @@ def main():
                          "projections, so the executed flops are 16 % below the reference's count used here")
 
     verify = ops_ms = None
-    if rank == 0 and world == 1 and fc_ws is None:
+    if rank == 0 and world == 1 and fc_ws is None and args.full:
         if not args.no_ref_gpu:
             verify = verify_against_reference(cfg, xb, kw, prm, D, ws, args.config)
         if not args.no_ops:
@@ -1029,13 +1070,13 @@ def main():
             ops_ms = round((time.perf_counter() - t0) / n * 1e3, 3)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config != "kitti_slow_fc":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.config != "kitti_slow_fc":
         # (kitti_slow_fc: the oracle's FC stack is a scalar triple loop, hours at this size; see kitti_slow)
         rows = args.cpu_rows or {"kitti_fast": 370, "kitti_slow": 370, "mb_slow": 64, "tiny": 48}[args.config]
         cpu = cpu_baseline(cfg, host, rows)
 
     north = kacc = kfc = fimg = pipe = None
-    if rank == 0 and world == 1 and args.config == "kitti_fast" and not args.no_north_star:
+    if rank == 0 and world == 1 and args.full and args.config == "kitti_fast" and not args.no_north_star:
         del ws, xb, kw
         torch.cuda.empty_cache()
         for name, fn in (("fimg", lambda: from_images_record(device)),
@@ -1063,7 +1104,9 @@ def main():
             "value": round(value, 1), "unit": "MPix-disp/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "ms_per_step_min": round(min(blocks) / args.steps * 1e3, 4), "timed_blocks": len(blocks), "timed_seconds": round(sum(blocks), 3),
-            "timing": "blocks of exactly %d steps between barrier + synchronise, repeated until >= %.1f s; value / ms_per_step = median block" % (args.steps, args.min_seconds),
+            "timing": ("blocks of exactly %d steps between barrier + synchronise, repeated until >= %.1f s; value / ms_per_step = median block" % (args.steps, args.min_seconds)
+                       if args.min_seconds > 0 else "exactly %d steps between barrier + synchronise" % args.steps),
+            "full": args.full,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "pair": PAIR_NOTE[pair],
             "config": {"workload": cfg_name, "H": H, "W": W, "disp_max": D, "feature_channels": abs(C),

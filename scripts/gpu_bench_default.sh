@@ -1,8 +1,8 @@
 #!/bin/bash
-# the driver's default line, on the GPU box: bash scripts/gpu_bench_default.sh <tag>
+# the default line with every side record (--full), on the GPU box: bash scripts/gpu_bench_default.sh <tag>
 ulimit -c 0
 O=$GRAFT_REPO_ROOT/gpurun_out/$1; mkdir -p $O
-SECONDS=0; timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$? wall=${SECONDS}s"
+SECONDS=0; timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$? wall=${SECONDS}s"
 python - <<PY
 import json
 l=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])

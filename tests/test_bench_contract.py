@@ -181,3 +181,23 @@ def test_conv_plan_splits_banks_that_do_not_fit():
     assert lib.mc_conv3x3_workspace_bytes(1, 64) == 2 * 64 * 9 * 2 * 4              # the pair count is padded to even
     assert lib.mc_conv3x3_workspace_bytes(112, 112) == 4 * 56 * 64 * 9 * 1 * 4      # four groups of 32 output channels (126 KB each)
     assert lib.mc_conv3x3_workspace_bytes(0, 64) == 0 and lib.mc_conv3x3_workspace_bytes(64, 129) == 0
+
+
+def test_dump_outputs_keeps_small_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per array; past the byte cap a fixed (seeded) sample of the elements with its flat indices"""
+    import numpy as np
+    import torch
+    b = _bench()
+    small = torch.arange(12, dtype=torch.float32).reshape(1, 1, 3, 4)
+    big = torch.linspace(0, 1, 5000, dtype=torch.float64)
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 4096)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), dict(disp=small, big=big))
+    s = np.load(tmp_path / "a" / "disp.npy")
+    assert s.dtype == np.float32 and s.shape == (1, 1, 3, 4) and (s == small.numpy()).all()
+    v, i = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "a" / "big_index.npy")
+    assert v.dtype == np.float32 and 0 < v.size < big.numel() and (np.diff(i) > 0).all()
+    assert (v == big.numpy().astype(np.float32)[i]).all()
+    assert s.nbytes + v.nbytes + i.nbytes <= 4096
+    for f in ("disp.npy", "big.npy", "big_index.npy"):
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()

@@ -16,7 +16,6 @@ int scale(const float *in, float *out, int64_t n, float s, hipStream_t st);
 int transpose(const float *in, float *out, int64_t R, int64_t Cn, int64_t ldin, int64_t ldout, float s, hipStream_t st, int nt = -1);
 int fix_border(float *vol, int D, int H, int W, int n, int direction, hipStream_t st);
 int argmin_dhw(const float *vol, float *out, int D, int H, int W, int base1, hipStream_t st);
-int argmin_hwd(const float *vol, float *out, int D, int ds, int H, int W, hipStream_t st);
 int outlier_detection(const float *d0, const float *d1, float *outlier, int H, int W, int disp_max, hipStream_t st);
 int interpolate_occlusion(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st);
 int interpolate_mismatch(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st);
@@ -433,11 +432,10 @@ static int predict_impl(const mc_params *p, const float *x0, const float *x1, co
 	}
 
 	// ---- argmin, main.lua:1049-1050 ----
+	// an (H,W,ds) volume exists only around the SGM, whose last up sweep folds the arg-min in where no CBCA-2 follows (have_disp)
+	MC_REQUIRE(have_disp || !hwd, "mc_predict: an (H,W,D) volume without its arg-min");
 	if (!have_disp) {
-		for (int v = 0; v < nvol; ++v) {
-			if (hwd) RUN(argmin_hwd(cur[v], dispv[v], D, ds, H, W, st));
-			else RUN(argmin_dhw(cur[v], dispv[v], D, H, W, 0, st));
-		}
+		for (int v = 0; v < nvol; ++v) RUN(argmin_dhw(cur[v], dispv[v], D, H, W, 0, st));
 	}
 	// ---- left.bin / right.bin contents, main.lua:1042-1047 ----
 	float *vout[2] = {volL_out, volR_out};

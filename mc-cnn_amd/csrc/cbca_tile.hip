@@ -938,19 +938,20 @@ static int cbca_tiles_launch_mode(CbcaArgs P, bool nt, hipStream_t st)
 	return check_launch("cbca_tile");
 }
 
-template <int A, int TW, int TH, int NWAVES>
+// PLANNED: the product's geometry of the instance (cfg.variant = 0), the only one mc_predict and the hook's plan forms 4 - 7 launch
+template <int A, int TW, int TH, int NWAVES, bool PLANNED = false>
 static int cbca_tiles_launch(CbcaArgs P, bool nt, int plan_mode, hipStream_t st)
 {
 	tile_regions(P.H, P.W, TW, TH, P.gx, P.gy, P.rb);
 	P.spr = P.rb / TH;
 	const PlanLayout L = plan_layout(P.D, P.H, P.W);
 	P.plan_m = L.m; P.plan_ud = L.ud; P.wp = L.wp;
-	if constexpr (TW == PLAN_TW && TH == PLAN_TH) {
-		static_assert(TileGeo<A, TW, TH>::ENT_BYTES == TileGeo<4, PLAN_TW, PLAN_TH>::ENT_BYTES, "one plan layout");
+	if constexpr (PLANNED) {
+		static_assert(TW == PLAN_TW && TH == PLAN_TH && TileGeo<A, TW, TH>::ENT_BYTES == TileGeo<4, PLAN_TW, PLAN_TH>::ENT_BYTES, "one plan layout");
 		if (plan_mode == 1) return cbca_tiles_launch_mode<A, TW, TH, NWAVES, 1>(P, nt, st);
 		if (plan_mode == 2) return cbca_tiles_launch_mode<A, TW, TH, NWAVES, 2>(P, nt, st);
 	}
-	return cbca_tiles_launch_mode<A, TW, TH, NWAVES, 0>(P, nt, st);   // (other geometries: no plan)
+	return cbca_tiles_launch_mode<A, TW, TH, NWAVES, 0>(P, nt, st);   // (the tuning hook's other geometries: no plan)
 }
 
 // arm_class 4: every arm <= 4 (L1 <= 5); 13: every arm <= 13 (L1 <= 14).  route >= 0 (the caller does not know the arms): the
@@ -982,14 +983,14 @@ int cbca_tiles(const void *packed, const float *vin, float *vout, int D, int H, 
 		case 1: return cbca_tiles_launch<4, 128, 32, 8>(P, nt, pm, st);
 		case 2: return cbca_tiles_launch<4, 128, 32, 4>(P, nt, pm, st);
 		case 3: return cbca_tiles_launch<4, 256, 16, 8>(P, nt, pm, st);
-		default: return cbca_tiles_launch<4, 128, 16, 4>(P, nt, pm, st);
+		default: return cbca_tiles_launch<4, 128, 16, 4, true>(P, nt, pm, st);
 		}
 	}
 	switch (cfg.variant) {
 	case 1: return cbca_tiles_launch<13, 128, 32, 8>(P, nt, pm, st);
 	case 2: return cbca_tiles_launch<13, 128, 16, 4>(P, nt, pm, st);
 	case 3: return cbca_tiles_launch<13, 64, 16, 4>(P, nt, pm, st);
-	default: return cbca_tiles_launch<13, 128, 16, 8>(P, nt, pm, st);
+	default: return cbca_tiles_launch<13, 128, 16, 8, true>(P, nt, pm, st);
 	}
 }
 

@@ -273,11 +273,15 @@ __global__ void __launch_bounds__(256) conv3x3_kernel(const float *__restrict__ 
 				for (int t = 0; t < NT; ++t) {
 #pragma unroll
 					for (int i = 0; i < 16; ++i) {
-						const uint32_t cpl = (uint32_t)(co0 + t * 32 + (i & 3) + 8 * (i >> 2)) * plane;   // wave-uniform
+						const int cb = co0 + t * 32 + (i & 3) + 8 * (i >> 2);   // wave-uniform; the lane's channel is cb + 4 * kh
+						// cb >= Cout: a padded channel in both half-waves, skipped as a whole -- cb * plane (up to tiles * 32 - 1
+						// planes) may exceed 2^32, and wrapped modulo 2^32 it would land inside the output, on a real channel
+						if (cb >= Cout) continue;
+						const uint32_t cpl = (uint32_t)cb * plane;   // < Cout * plane < 2^32 (api.hip)
 						const float v = acc[r][t][i];
-						// the buffer ends with channel Cout - 1, which drops the padded channels; o0 + cpl stays below 2^32 for every
-						// lane that must store (api.hip checks Cout * plane), and a lane holding CV_OOB must stay out of range:
-						// saturate instead of wrapping
+						// the buffer ends with channel Cout - 1, which drops the padded channels cb + 4 of the upper half-wave; o0 + cpl
+						// stays below 2^32 for every lane that must store (api.hip checks Cout * plane), and a lane holding CV_OOB must
+						// stay out of range: saturate instead of wrapping
 						const uint32_t off = o0 > CV_OOB - cpl ? CV_OOB : o0 + cpl;
 						__builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(RELU ? relu1(v) : v), ro, off, 0, 0);
 					}

@@ -191,30 +191,6 @@ __global__ void __launch_bounds__(256) argmin_dhw4_kernel(const float *__restric
 	*(post_f4 *)(out + p) = post_f4{(float)(a0 + base1), (float)(a1 + base1), (float)(a2 + base1), (float)(a3 + base1)};
 }
 
-// (H,W,ds) layout: one wave per pixel, lanes over d.
-__global__ void __launch_bounds__(256) argmin_hwd_kernel(const float *__restrict__ vol, float *__restrict__ out, int D, int ds,
-                                                         int64_t HW)
-{
-	const int lane = threadIdx.x & 63;
-	const int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-	if (p >= HW) return;
-	const float INF = __builtin_inff();
-	float best = INF;
-	int bi = 0;
-	for (int d = lane; d < D; d += 64) {  // ascending d per lane keeps "first" semantics
-		const float val = vol[p * ds + d];
-		if (val < best) {
-			best = val;
-			bi = d;
-		}
-	}
-	const float mall = wave_min(best);
-	// smallest index among lanes holding the minimum
-	int cand = (best == mall && best < INF) ? bi : 0x7fffffff;
-	for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o));
-	if (lane == 0) out[p] = (float)(cand == 0x7fffffff ? 0 : cand);
-}
-
 int argmin_dhw(const float *vol, float *out, int D, int H, int W, int base1, hipStream_t st)
 {
 	const int64_t HW = (int64_t)H * W;
@@ -223,13 +199,6 @@ int argmin_dhw(const float *vol, float *out, int D, int H, int W, int base1, hip
 	else
 		hipLaunchKernelGGL(argmin_dhw_kernel, dim3(cdiv(HW, 256)), dim3(256), 0, st, vol, out, D, HW, base1);
 	return check_launch("argmin_dhw");
-}
-
-int argmin_hwd(const float *vol, float *out, int D, int ds, int H, int W, hipStream_t st)
-{
-	const int64_t HW = (int64_t)H * W;
-	hipLaunchKernelGGL(argmin_hwd_kernel, dim3(cdiv(HW * 64, 256)), dim3(256), 0, st, vol, out, D, ds, HW);
-	return check_launch("argmin_hwd");
 }
 
 // ---- outlier_detection, adcensus.cu:878-899 ------------------------------------------------

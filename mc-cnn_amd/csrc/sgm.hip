@@ -493,21 +493,26 @@ static void launch_pass(const SgmPassArgs &A, bool vec, hipStream_t st)
 	// sweep (three loads per step) at 16 throughout; 1500x1000x256 within 1 % either way.  The sweeps run at what the
 	// memory system gives long-lived waves that each walk their own line (4.3-5.1 TB/s), not at a latency bound.
 	const int U = DIRN == 2 ? SGM_U_DOWN : (DIRN == 3 ? SGM_U_UP : SGM_U_H);
+	// MODE 1 (mc_sgm2, the caller's volumes) has the per-element instances for an unaligned volume or a pixel stride that is not a
+	// multiple of 4; the fused modes run on mc_predict's workspace only (ds = Dp, 256-byte aligned slices: sgm_sweeps requires vec)
+	constexpr bool SCALAR = MODE == 1;
 #define MC_SGM_GO(VPL_, VEC_, U_) \
 	hipLaunchKernelGGL((sgm_pass_kernel<DIRN, VPL_, MODE, ARGMIN, VEC_, U_, DUAL, false>), grid, block, 0, st, A)
 #define MC_SGM_GO_FAR(VPL_, VEC_, U_) \
 	hipLaunchKernelGGL((sgm_pass_kernel<DIRN, VPL_, MODE, ARGMIN, VEC_, U_, DUAL, true>), grid, block, 0, st, A)
 	// a volume of 2 GiB or more: 64-bit pixel addresses in every step (one prefetch depth only)
 	const bool far = (int64_t)A.H * A.W * A.ds * 4 >= ((int64_t)1 << 31);
-	if (far) {
-		if (A.D <= 256) { if (vec) MC_SGM_GO_FAR(4, true, 4); else MC_SGM_GO_FAR(4, false, 4); }
-		else { if (vec) MC_SGM_GO_FAR(8, true, 4); else MC_SGM_GO_FAR(8, false, 2); }
+	if (!vec) {
+		if constexpr (SCALAR) {
+			if (far) { if (A.D <= 256) MC_SGM_GO_FAR(4, false, 4); else MC_SGM_GO_FAR(8, false, 2); }
+			else { if (A.D <= 256) MC_SGM_GO(4, false, 4); else MC_SGM_GO(8, false, 2); }
+		}
+	} else if (far) {
+		if (A.D <= 256) MC_SGM_GO_FAR(4, true, 4); else MC_SGM_GO_FAR(8, true, 4);
 	} else if (A.D <= 256) {
-		if (vec) { if (U == 16) MC_SGM_GO(4, true, 16); else if (U == 8) MC_SGM_GO(4, true, 8); else MC_SGM_GO(4, true, 4); }
-		else MC_SGM_GO(4, false, 4);
+		if (U == 16) MC_SGM_GO(4, true, 16); else if (U == 8) MC_SGM_GO(4, true, 8); else MC_SGM_GO(4, true, 4);
 	} else {
-		if (vec) { if (U >= 8) MC_SGM_GO(8, true, 8); else MC_SGM_GO(8, true, 4); }
-		else MC_SGM_GO(8, false, 2);
+		if (U >= 8) MC_SGM_GO(8, true, 8); else MC_SGM_GO(8, true, 4);
 	}
 #undef MC_SGM_GO_FAR
 #undef MC_SGM_GO
@@ -518,7 +523,8 @@ static void launch_pass(const SgmPassArgs &A, bool vec, hipStream_t st)
 //   fused = false: every sweep does out += L_r (adcensus.sgm2 contract, out pre-zeroed by caller)
 //   fused = true : right and left sweeps run concurrently (out = 0 + L_0, out2 = L_1), the down sweep
 //                  writes (out + out2) + L_2 to out, the up sweep writes (out + L_3)/4 and, if disp[] is
-//                  set, the argmin of the finished pixel.  `out2` is scratch of the same size as out.
+//                  set, the argmin of the finished pixel.  `out2` is scratch of the same size as out (required),
+//                  ds % 4 == 0 and every volume 16-byte aligned (required: mc_predict's workspace).
 int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
                const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,
                float alpha1, float q1, float q2, bool fused, hipStream_t st)
@@ -554,15 +560,14 @@ int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2
 		if (out2) vec = vec && ((uintptr_t)out2[v] % 16 == 0);
 	}
 	const bool am = fused && disp && disp[0];
-	if (!fused || !out2) {
-		const bool f = fused;  // fused without scratch: sequential sweeps with the zero and /4 still folded
-		if (f) launch_pass<0, 0, false, false>(A, vec, st); else launch_pass<0, 1, false, false>(A, vec, st);
+	if (!fused) {
+		launch_pass<0, 1, false, false>(A, vec, st);
 		launch_pass<1, 1, false, false>(A, vec, st);
 		launch_pass<2, 1, false, false>(A, vec, st);
-		if (!f) launch_pass<3, 1, false, false>(A, vec, st);
-		else if (am) launch_pass<3, 2, true, false>(A, vec, st);
-		else launch_pass<3, 2, false, false>(A, vec, st);
+		launch_pass<3, 1, false, false>(A, vec, st);
 	} else {
+		// mc_predict: scratch for the concurrent second direction, and its own aligned (H,W,Dp) volumes
+		MC_REQUIRE(out2 && vec, "sgm: the fused sweeps need the second direction's scratch and 16-byte aligned volumes with ds %% 4 == 0");
 		launch_pass<0, 0, false, true>(A, vec, st);
 		launch_pass<2, 3, false, false>(A, vec, st);
 		if (am) launch_pass<3, 2, true, false>(A, vec, st);

@@ -410,7 +410,10 @@ int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, 
 	const int rows8 = (H + 7) / 8;
 	const int ks = (C + 1) / 2;
 	const dim3 block(256);
-	if (ds % 4 == 0 && (uintptr_t)volL % 16 == 0 && (uintptr_t)volR % 16 == 0 && ks <= 32) {
+	// mc_predict's (H,W,Dp) workspace volumes only: the owner kernel's 16-byte runs need them
+	MC_REQUIRE(ds % 4 == 0 && (uintptr_t)volL % 16 == 0 && (uintptr_t)volR % 16 == 0,
+	           "stereo_join_hwd: the volumes must be 16-byte aligned with a pixel stride ds %% 4 == 0 (ds = %d)", ds);
+	if (ks <= 32) {
 		const int tiles_own = ((W + 31) / 32 + MC_JOIN_NT - 1) / MC_JOIN_NT;   // groups of MC_JOIN_NT 32-pixel tiles per image row and volume
 		const dim3 grid_o((unsigned)(rows8 * ((2 * tiles_own + MC_JOIN_WPB - 1) / MC_JOIN_WPB) * 8)), block_o(64 * MC_JOIN_WPB);
 		if (ks <= 8) hipLaunchKernelGGL((join_owner_kernel<8>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own);
@@ -422,6 +425,7 @@ int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, 
 		hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)H * n * 64, 256)), block, 0, st, volR, D, ds, H, W, n, 1);
 		return check_launch("fix_border_hwd");
 	}
+	// C > 64 (ks > 32, MC_JOIN_MAX_C = 128: ks <= 64)
 	const int tiles = (W + D - 1 + 31) / 32;  // incl. the virtual tiles right of the image (right volume's NaN triangle)
 	const int blocks_per_row = (tiles + 3) / 4;
 	const dim3 grid((unsigned)(rows8 * blocks_per_row * 8));
@@ -429,10 +433,7 @@ int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, 
 	do {                                                                                                                    \
 		hipLaunchKernelGGL((join_mfma_kernel<KS>), grid, block, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles);             \
 	} while (0)
-	if (ks <= 8) MC_JOIN_LAUNCH(8);
-	else if (ks <= 16) MC_JOIN_LAUNCH(16);
-	else if (ks <= 32) MC_JOIN_LAUNCH(32);
-	else if (ks <= 56) MC_JOIN_LAUNCH(56);
+	if (ks <= 56) MC_JOIN_LAUNCH(56);
 	else MC_JOIN_LAUNCH(64);
 #undef MC_JOIN_LAUNCH
 	int rc = check_launch("stereo_join_hwd");

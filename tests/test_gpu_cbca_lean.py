@@ -48,7 +48,8 @@ def test_lean_and_list(mc, oracle, H, W, D, mk, L1, tau1):
 
 
 @pytest.mark.parametrize("rb", [0, 2, 4, 8, 5])          # rows per wave (anything but 2 / 4 / 8: the product's choice)
-@pytest.mark.parametrize("variant", [0, 4, 16, 20, 96])   # bit 2: the listed outputs in a launch of their own, bit 4: a band of rows per XCD, bits 5 / 6: non-temporal loads / stores
+@pytest.mark.parametrize("variant", [0, 4, 16, 20, 96, 32, 36, 64, 68, 100])   # bit 2: the listed outputs in a launch of their own, bit 4: a band of rows per XCD, bits 5 / 6: non-temporal loads / stores
+                                                                           # (every cbca_lean_kernel<rows, policy, listed-in-the-same-launch>)
 def test_lean_rows_per_wave_and_launch_variants(mc, oracle, rb, variant):
     H, W, D = 61, 530, 5
     x0, x1 = smooth_pair(H, W, 8, seed=3)

@@ -57,7 +57,7 @@ def test_two_passes_in_one_launch(mc, oracle, H, W, D, mk, L1, tau1):
 
 
 @pytest.mark.parametrize("H,W,D", [(61, 530, 5), (90, 300, 9), (5, 7, 3), (17, 257, 9), (3, 1030, 5), (140, 130, 3), (1, 9, 2), (25, 760, 3)])
-@pytest.mark.parametrize("rb", [0, 4, 8, 12, 5])   # rows per wave (anything but 4 / 8 / 12: the product's choice)
+@pytest.mark.parametrize("rb", [0, 4, 8, 12, 5, 6, 10])   # rows per wave (anything but 4 / 6 / 8 / 10 / 12: the product's choice)
 @pytest.mark.parametrize("mk,L1,tau1", [("smooth", 14, 0.05), ("blocky", 14, 0.2), ("natural", 14, 0.02)])
 def test_two_pass_wave_geometries(mc, oracle, H, W, D, rb, mk, L1, tau1):
     x0, x1 = pair(mk, H, W, D)

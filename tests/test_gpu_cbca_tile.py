@@ -55,6 +55,23 @@ def test_tile_kernel_long_arms(mc, oracle, H, W, D, mk, L1, tau1):
         assert same_bits(got, want), diff_report(got, want, "tile kernel (arms <= 13) dir=%d" % direction)
 
 
+@pytest.mark.parametrize("form,L1,tau1", [(2, 5, 0.13), (3, 14, 0.02)])
+@pytest.mark.parametrize("variant", [1, 2, 3])   # the geometry variants of the tuning hook (cbca_tiles: cfg.variant), each instance
+@pytest.mark.parametrize("nt", [0, 1])
+def test_tile_kernel_geometry_variants(mc, oracle, form, L1, tau1, variant, nt):
+    for H, W, D in ((37, 449, 4), (17, 257, 9)):
+        x0, x1 = pair("natural", H, W, D)
+        x0c, x1c = oracle.cross(x0, L1, tau1), oracle.cross(x1, L1, tau1)
+        vl, vr = raw_volumes(D, H, W, seed=13)
+        for direction, vol in ((-1, vl), (1, vr)):
+            want = oracle.cbca(x0c, x1c, vol, direction)
+            out = torch.full((1, D, H, W), -7.0, device="cuda")
+            mc.adcensus.cbca_cfg(dev(x0c), dev(x1c), dev(vol), out, direction, rb=variant, nt=nt, form=form)
+            got = out.cpu().numpy()
+            assert same_bits(got, want), diff_report(got, want, "tile kernel form %d variant %d nt %d %dx%dx%d dir=%d" % (
+                form, variant, nt, H, W, D, direction))
+
+
 @pytest.mark.parametrize("form,L1", [(2, 5), (3, 14)])
 def test_tile_kernel_plane_range(mc, oracle, form, L1):
     H, W, D = 30, 200, 21

@@ -22,6 +22,14 @@ torch = pytest.importorskip("torch")
     (3, 8, 64, 61, 33, False),       # runs that cross columns and images, tiles of 1 .. 4 rows
     (1, 64, 64, 300, 100, True),     # every wave of the launch busy, several tiles per wave, short last tiles
     (1, 112, 112, 130, 70, True),    # the same for the four-group split (tiles of 8 rows)
+    # the instantiation each case plans (conv3x3.hip: conv_plan) is named below; the cases above plan <2, *, false> and <1, true, *>
+    (2, 8, 32, 19, 70, False),       # <1, false, false>: one tile of 32 output channels, no ReLU
+    (1, 40, 96, 11, 45, False),      # <1, false, false>: three groups of 32, no ReLU
+    (1, 141, 40, 9, 70, False),      # <1, false, true>: the smallest Cin whose 32-channel bank does not fit (72 pairs), no ReLU
+    (3, 8, 33, 21, 40, False),       # <2, false, false>: Cout % 8 != 0 (the per-channel store path), three images
+    (3, 8, 100, 13, 70, True),       # <2, true, false>: two groups of 64, the second with 36 of 64 channels, three images
+    (3, 150, 33, 9, 40, True),       # <1, true, true>: chunked, Cout % 8 != 0, three images
+    (3, 150, 100, 7, 35, False),     # <1, false, true>: chunked, four groups of 32, the last with 4 channels, three images
 ])
 def test_conv3x3_vs_torch(mc, N, Cin, Cout, H, W, relu):
     import torch.nn.functional as F
@@ -55,3 +63,34 @@ def test_feature_nets_run_on_the_hand_written_convolution(mc):
     assert f.shape == (2, 64, 24, 50)
     n = (f.double() ** 2).sum(1)
     assert float((n - 1).abs().max()) < 1e-3     # Normalize2: unit-norm feature vectors (eps 1e-5 inside the root)
+
+
+@pytest.mark.parametrize("Cout,H,W,relu", [
+    (33, 4000, 5000, False),   # <2, false, false>: padded channels up to 63, 63 * H * W * 4 > 2^32
+    (100, 3000, 3300, True),   # <2, true, false>: two groups, padded channels up to 127, 127 * H * W * 4 > 2^32
+])
+def test_conv3x3_padded_channels_do_not_wrap(mc, Cout, H, W, relu):
+    """The per-channel store path (Cout % 8 != 0) at images where a padded channel's byte offset, channel * H * W * 4, exceeds 2^32
+    while Cout * H * W * 4 does not (mc_conv3x3 accepts the shape): the padded channels' stores must be dropped, not wrap round
+    onto real channels.  One input channel, so that the float64 reference is nine shifted multiply-adds on the device,
+    channel by channel."""
+    import torch.nn.functional as F
+    assert (Cout * H * W * 4 < 1 << 32) and ((Cout + 31) // 32 * 32 - 1) * H * W * 4 >= 1 << 32
+    g = torch.Generator(device="cuda").manual_seed(Cout)
+    x = torch.randn((1, 1, H, W), device="cuda", generator=g)
+    w = torch.rand((Cout, 1, 3, 3), device="cuda", generator=g) * 2 - 1
+    b = torch.rand((Cout,), device="cuda", generator=g) * 2 - 1
+    got = mc.adcensus.conv3x3(x, w, b, relu)
+    xp = F.pad(x[0, 0].double(), (1, 1, 1, 1))
+    wd, bd = w.double().cpu(), b.double().cpu()
+    err = scale = 0.0
+    for co in range(Cout):
+        want = torch.full((H, W), float(bd[co]), dtype=torch.float64, device="cuda")
+        for ky in range(3):
+            for kx in range(3):
+                want.add_(xp[ky:ky + H, kx:kx + W], alpha=float(wd[co, 0, ky, kx]))
+        if relu:
+            want.clamp_(min=0)
+        err = max(err, float((got[0, co].double() - want).abs().max()))
+        scale = max(scale, float(want.abs().max()))
+    assert err <= 1e-4 * max(1.0, scale), "max |diff| = %g (scale %g)" % (err, scale)

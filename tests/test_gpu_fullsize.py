@@ -86,3 +86,61 @@ def test_fused_predict_on_real_scene_arm_statistics(ref, mc, preset, H, W, D):
     torch.cuda.synchronize()
     for key, label in (("volL", "left.bin"), ("volR", "right.bin"), ("dispL0", "left argmin"), ("dispR0", "right argmin"), ("disp", "disp.bin")):
         assert_same_bits_dev(got[key], want[key], "%s %s on the realistic pair" % (preset, label))
+
+
+def _device_pair(H, W, seed):
+    """a textured pair made on the device (no multi-GB host arrays): smoothed noise, the right image the left shifted by 9 pixels"""
+    import torch.nn.functional as F
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    x0 = F.avg_pool2d(torch.rand((1, 1, H, W + 16), device="cuda", generator=g), 3, 1, 1)
+    x1 = torch.roll(x0, -9, dims=3) + 0.02 * torch.rand(x0.shape, device="cuda", generator=g)
+    return torch.cat([x0, x1])[:, :, :, :W].contiguous()
+
+
+def _device_raw_volumes(D, H, W, seed):
+    """tests/util.raw_volumes on the device: uniform [0, 1) with the NaN triangles (left d > x, right x + d >= W)"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    d = torch.arange(D, device="cuda")[:, None, None]
+    x = torch.arange(W, device="cuda")[None, None, :]
+    vl = torch.rand((1, D, H, W), device="cuda", generator=g).masked_fill_((d > x)[None], float("nan"))
+    vr = torch.rand((1, D, H, W), device="cuda", generator=g).masked_fill_((x + d >= W)[None], float("nan"))
+    return vl, vr
+
+
+def _device_features(C, H, W, seed):
+    """tests/util.features on the device: N(0, 1) L2-normalised over C, the right view the left shifted by 9 pixels plus noise"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    f0 = torch.randn((1, C, H, W), device="cuda", generator=g)
+    f1 = torch.roll(f0, -9, dims=3) + 0.3 * torch.randn(f0.shape, device="cuda", generator=g)
+    f = torch.cat([f0, f1])
+    return (f / torch.sqrt((f.double() ** 2).sum(1, keepdim=True) + 1e-5).float()).contiguous()
+
+
+@pytest.mark.parametrize("preset,over,H,W,D,C", [
+    # the fused sweeps on volumes of 2 GiB or more (sgm.hip: the FAR = 64-bit-address instances), 4 and 8 disparities per lane:
+    # the two horizontal directions at once (MODE 0, DUAL), the down sweep (MODE 3), the up sweep with the arg-min folded in
+    # (MODE 2, ARGMIN: cbca_i2 = 0) and without it (cbca_i2 > 0: CBCA-2 and the arg-min follow)
+    ("kitti_fast", {}, 1400, 1536, 256, 16),
+    ("kitti_ad", {"cbca_i2": 2}, 1400, 1536, 256, 0),
+    ("kitti_fast", {}, 1000, 1500, 360, 16),
+    ("kitti_ad", {"cbca_i2": 2}, 1000, 1500, 360, 0),
+])
+def test_fused_predict_on_volumes_of_two_gib(ref, mc, preset, over, H, W, D, C):
+    """mc_predict where every (H,W,Dp) volume spans 2 GiB or more, against main.lua's stereo_predict over the reference's kernels,
+    compared on the device"""
+    from ref_pipeline import ref_stereo_predict
+    from mc_cnn_amd.predict import Workspace
+    assert H * W * ((D + 3) // 4 * 4) * 4 >= 1 << 31
+    prm = dict(mc.PRESETS[preset])
+    prm.update(over)
+    xb = _device_pair(H, W, seed=H + D)
+    kw = dict(feat=_device_features(C, H, W, seed=D)) if C else dict(raw=_device_raw_volumes(D, H, W, seed=D))
+    ws = Workspace(prm, D, H, W, xb.device)
+    got = mc.stereo_predict_fused(xb, prm, D, workspace=ws, want_volumes=True, want_disp0=True, **kw)
+    torch.cuda.synchronize()
+    del ws
+    want = ref_stereo_predict(ref, prm, xb, D, **kw)
+    torch.cuda.synchronize()
+    for key, label in (("volL", "left.bin"), ("volR", "right.bin"), ("dispL0", "left argmin"),
+                       ("dispR0", "right argmin"), ("disp", "disp.bin")):
+        assert_same_bits_dev(got[key], want[key], "%s %dx%dx%d %s: hip fused vs reference kernels" % (preset, H, W, D, label))

@@ -130,7 +130,7 @@ SGM_PARAMS = [  # pi1, pi2, tau_so, alpha1, q1, q2
 ]
 
 
-@pytest.mark.parametrize("H,W,D", SHAPES)
+@pytest.mark.parametrize("H,W,D", SHAPES + [(6, 300, 261)])   # (6, 300, 261): 8 per lane with D % 4 != 0, the per-element loads
 @pytest.mark.parametrize("prm", SGM_PARAMS)
 @pytest.mark.parametrize("direction", [-1, 1])
 def test_sgm2(mc, oracle, H, W, D, prm, direction):
@@ -216,16 +216,54 @@ def test_post_chain(mc, oracle, H, W, D):
     sub = mc.adcensus.subpixel_enchancement(mis, dev(vl)[None], D)
     want_sub = oracle.subpixel_enchancement(want_mis, vl)
     assert_same(host(sub), want_sub, "subpixel")
-    for k in (1, 3, 5, 11):
+    for k in (1, 3, 5, 7, 9, 11):   # median_kernel<k / 2>: every instance
         med = mc.adcensus.median2d(sub, k)
         assert_same(host(med), oracle.median2d(want_sub, k), "median%d" % k)
     med = mc.adcensus.median2d(sub, 5)
     want_med = oracle.median2d(want_sub, 5)
-    for sigma, t in ((1.0, 2.0), (1.67, 2.0), (2.78, 3.0), (4.64, 5.0), (5.99, 6.0), (7.74, 5.0)):   # 1.0: the run-time-size kernel
+    # 1.0, 12, 20: the run-time-size kernel -- at 12 (73 x 73) its LDS just exceeds 64 KiB (hipFuncSetAttribute), at 20 (121 x 121) it
+    # needs 151 KiB of the 160
+    for sigma, t in ((1.0, 2.0), (1.67, 2.0), (2.78, 3.0), (4.64, 5.0), (5.99, 6.0), (7.74, 5.0), (12.0, 3.0), (20.0, 4.0)):
         k = mc.adcensus.gaussian(sigma)
         assert_same(k.numpy(), oracle.gaussian(sigma), "gaussian")
         got = mc.adcensus.mean2d(med, k.cuda(), t)
         assert_same(host(got), oracle.mean2d(want_med, oracle.gaussian(sigma), t), "mean2d sigma=%g" % sigma)
+
+
+@pytest.mark.parametrize("H,W", [(1, 30), (3, 4), (8, 100), (40, 13), (25, 70)])
+def test_median_ties_and_edges(mc, oracle, H, W):
+    """median2d at k = 7 and 9 (median_kernel<3>, <4>) beside the others: integer images of few values (ties everywhere), windows
+    cut by every image edge, images narrower or lower than the window"""
+    rng = np.random.default_rng(H * 100 + W)
+    img = rng.integers(0, 4, (H, W)).astype(np.float32)
+    img[rng.random((H, W)) < 0.2] = 2.5
+    for k in (1, 3, 5, 7, 9, 11):
+        assert_same(host(mc.adcensus.median2d(dev(img)[None, None], k)), oracle.median2d(img, k), "median%d ties %dx%d" % (k, H, W))
+
+
+def test_mean2d_refuses_kernels_beyond_lds(mc):
+    """sigma = 21 (a 127 x 127 kernel) needs more LDS than a CU has: mc_mean2d and mc_predict return MC_EINVAL with a message and
+    write no output"""
+    import ctypes
+    lib = mc._lib.lib
+    H, W = 16, 40
+    img = torch.rand((1, 1, H, W), device="cuda")
+    k = mc.adcensus.gaussian(21.0).cuda()
+    assert k.shape == (127, 127)
+    out = torch.full((1, 1, H, W), 1234.5, device="cuda")
+    assert lib.mc_mean2d(img.data_ptr(), k.data_ptr(), out.data_ptr(), H, W, 127, ctypes.c_float(3.0), None) == -22
+    assert b"LDS" in lib.mc_last_error()
+    torch.cuda.synchronize()
+    assert bool((out == 1234.5).all())
+    with pytest.raises(mc._lib.McError, match="LDS"):
+        mc.adcensus.mean2d(img, k, 3.0)
+    prm = dict(mc.PRESETS["kitti_fast"], blur_sigma=21.0)
+    x0, x1 = smooth_pair(H, W, 8, seed=3)
+    out = torch.full((1, 1, H, W), 1234.5, device="cuda")
+    with pytest.raises(mc._lib.McError, match="LDS"):
+        mc.stereo_predict_fused(dev(np.stack([x0, x1]))[:, None], prm, 8, feat=dev(features(8, H, W, seed=4)), out=out)
+    torch.cuda.synchronize()
+    assert bool((out == 1234.5).all()), "mc_predict wrote disp.bin although it failed"
 
 
 def test_mismatch_all_outliers(mc, oracle):
@@ -268,6 +306,17 @@ def test_sgm2_contract_check(mc, monkeypatch):
     mc.adcensus.sgm2(x, x, dev(hwd), out, torch.empty(1, device="cuda"), 1.0, 8.0, 0.1, 2.0, 3.0, 2.0, -1)
 
 
+@pytest.mark.parametrize("C", [7, 112, 130])   # normalize_kernel<64> (C <= 64), <128> (C <= 128), <0> (any C)
+def test_normalize_widths(mc, oracle, C):
+    rng = np.random.default_rng(9 + C)
+    x = rng.standard_normal((2, C, 11, 23)).astype(np.float32)
+    x[1, :, 3, 4] = 0.0                          # a zero feature vector: norm = the 1e-5 alone
+    out = torch.empty_like(dev(x))
+    norm = torch.empty((2, 1, 11, 23), device="cuda")
+    mc.adcensus.Normalize_forward(dev(x), norm, out)
+    assert_same(host(out), oracle.normalize_forward(x), "normalize C=%d" % C)
+
+
 def test_normalize_fix_border(mc, oracle):
     rng = np.random.default_rng(9)
     x = rng.standard_normal((2, 16, 11, 23)).astype(np.float32)
@@ -308,6 +357,12 @@ PRED_CASES = [
     ("mb_slow", {"cbca_i2": 3}, 28, 80, 20, 0),
     ("mb_slow", {"cbca_i2": 2}, 28, 80, 20, 32),  # features through the (D,H,W) + cbca route
     ("kitti_fast", {}, 8, 300, 260, 4),           # D > 256: 8 disparities per lane
+    ("kitti_slow", {"cbca_i2": 1}, 8, 300, 260, 0),   # D > 256 with CBCA-2: the up sweep without the folded arg-min, 8 per lane
+    ("kitti_fast", {"median_k": 7}, 24, 80, 20, 16),   # median_kernel<3> in the pipeline
+    ("kitti_fast", {}, 20, 72, 26, 24),          # 16 < C <= 32: join_owner_kernel<16>
+    ("kitti_fast", {}, 20, 70, 30, 65),          # C > 64: StereoJoin by join_mfma_kernel<56> (ks = 33)
+    ("kitti_fast", {}, 18, 64, 21, 112),         # join_mfma_kernel<56> at the slow nets' width, D % 4 != 0
+    ("kitti_fast", {}, 16, 90, 24, 128),         # join_mfma_kernel<64> (ks = 64, MC_JOIN_MAX_C)
 ]
 
 

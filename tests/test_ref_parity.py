@@ -145,6 +145,33 @@ def test_sgm2_volume_of_two_gib(ref, mc):
     assert same_dev, "hip sgm2 (2.2 GB volume) differs from the reference's kernels"
 
 
+@pytest.mark.parametrize("H,W,D", [
+    (1000, 1500, 360),   # 8 disparities per lane, 16-byte runs: sgm_pass_kernel<*, 8, 1, false, true, 4, false, true>
+    (1000, 1500, 361),   # 8 per lane, D % 4 != 0: the per-element instances <*, 8, 1, false, false, 2, false, true>
+    (560, 3840, 255),    # 4 per lane, D % 4 != 0: <*, 4, 1, false, false, 4, false, true>
+])
+def test_sgm2_volumes_of_two_gib_all_widths(ref, mc, H, W, D):
+    """The op-by-op sgm2 (MODE 1, pixel stride D) on the other FAR instances: D > 256 and D % 4 != 0 at 2 GiB or more, against the
+    reference's kernels on the same device tensors, compared on the device"""
+    assert H * W * D * 4 >= 1 << 31
+    g = torch.Generator(device="cuda").manual_seed(D)
+    x0 = torch.rand((1, 1, H, W), device="cuda", generator=g)
+    x1 = torch.rand((1, 1, H, W), device="cuda", generator=g)
+    vol = torch.rand((1, H, W, D), device="cuda", generator=g)
+    d = torch.arange(D, device="cuda")[None, None, None, :]
+    xx = torch.arange(W, device="cuda")[None, None, :, None]
+    vol.masked_fill_(xx + d >= W, float("nan"))              # the NaN triangle of a right volume
+    prm = (4.0, 55.72, 0.02, 1.5, 3.0, 2.5)
+    r = torch.zeros_like(vol)
+    tmp = torch.empty((W, D), device="cuda")
+    ref.call("sgm2", x0[0], x1[0], vol, r, tmp, *prm, 1)
+    got = torch.zeros_like(vol)
+    mc.adcensus.sgm2(x0[0, 0], x1[0, 0], vol, got, None, *prm, 1)
+    torch.cuda.synchronize()
+    same_dev = bool(((got.view(torch.int32) == r.view(torch.int32)) | (torch.isnan(got) & torch.isnan(r))).all().item())
+    assert same_dev, "hip sgm2 (%dx%dx%d) differs from the reference's kernels" % (H, W, D)
+
+
 @pytest.mark.parametrize("H,W,D", SHAPES[:4])
 def test_spatial_argmin(ref, mc, oracle, H, W, D):
     vl, _ = raw_volumes(D, H, W, seed=31)
@@ -198,7 +225,7 @@ def test_post_chain(ref, mc, oracle, H, W, D):
     same(oracle.subpixel_enchancement(host(rmis)[0, 0], vl), host(rsub), "oracle subpixel vs reference")
     same(host(mc.adcensus.subpixel_enchancement(rmis, dev(vl)[None], D)), host(rsub), "hip subpixel vs reference")
 
-    for k in (1, 3, 5, 11):
+    for k in (1, 3, 5, 7, 9, 11):
         rmed = ref.call("median2d", rsub, k)[0]
         same(oracle.median2d(host(rsub)[0, 0], k), host(rmed), "oracle median%d vs reference" % k)
         same(host(mc.adcensus.median2d(rsub, k)), host(rmed), "hip median%d vs reference" % k)

@@ -1,0 +1,544 @@
+// Training of the fast architecture (main.lua:602-890, arch fast on kitti / kitti2015) on gfx950: libmctrain.so.
+//
+// A step of the reference is ~15 cuDNN / THC launches (make_patch on the host, copy, forward of 4 convolutions, 3 ReLUs,
+// Normalize2, StereoJoin1, Margin2, and their backward passes, then 16 tensor updates).  The work is tiny (~2 GFLOP for
+// bs = 128), so here a step is TWO kernels:
+//   (a) train_step_kernel: one workgroup per training pair.  It samples the pair's three distinct patches (left,
+//       positive, negative; patches 4i-3 and 4i-1 of the reference's batch are drawn with identical arguments,
+//       main.lua:843,845) straight from the device-resident images into LDS, runs the forward pass, Normalize2,
+//       StereoJoin1, Margin2 and the whole backward pass with every activation in LDS, and writes the pair's weight and
+//       bias gradients to its own row of a slab (no float atomics).
+//   (b) train_sgd_kernel: sums the slab's rows in a fixed order (pair 0, 1, ...), applies  v = mom * v - lr * g;
+//       w += v  (main.lua:870-874) and writes the step's mean loss.  The fixed order makes a run bitwise reproducible.
+// The convolution GEMMs run on v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate -- the reference's precision):
+//   forward  out[co, p]      = sum_{ci,tap} W[co, ci, tap] * in[ci, p + tap]          (M = 64, N = pixels, K = 576)
+//   weights  dW[co, ci, tap] = sum_p g[co, p] * in[ci, p + tap]                        (M = 64, N = 576, K = pixels)
+//   data     dX[ci, q]       = sum_{co,tap} W[co, ci, tap] * g[co, q - tap]  (masked by ReLU)  (M = 64, N = pixels, K = 576)
+// The weights are read from global memory (L2-resident: 445 KB), the activations from LDS.  dX overwrites the
+// activation it is masked by, in place: a layer's activations are dead once its weight gradient is taken.
+// GEMMs with only two 32 x 32 output tiles (layer 3 / 4 forward, layer 4 data gradient) split K over four waves and
+// add the partial tiles in a fixed order.
+#include "mc_common.h"
+#include "../../include/mc_train.h"
+
+#include <stdarg.h>
+
+namespace mc {
+
+static thread_local char g_train_err[512] = "";
+
+void set_error(const char *fmt, ...)
+{
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(g_train_err, sizeof(g_train_err), fmt, ap);
+	va_end(ap);
+}
+
+int check_launch(const char *what)
+{
+	const hipError_t e = hipPeekAtLastError();
+	if (e != hipSuccess) {
+		set_error("%s: %s", what, hipGetErrorString(e));
+		return (int)e;
+	}
+	return 0;
+}
+
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+constexpr int FM = MC_TRAIN_FM;
+constexpr int WS = MC_TRAIN_WS;
+constexpr int NPRM = MC_TRAIN_NPRM;
+constexpr int NPARAMS = MC_TRAIN_NPARAMS;
+constexpr int NW = 8;                    // waves per workgroup (two per SIMD)
+constexpr int NT = NW * 64;
+
+// offsets of the flat parameter buffer: w1 b1 w2 b2 w3 b3 w4 b4
+constexpr int OFF_W1 = 0, OFF_B1 = FM * 9;
+constexpr int OFF_W2 = OFF_B1 + FM;
+constexpr int LAYER_STRIDE = FM * FM * 9 + FM;
+__host__ __device__ constexpr int off_w(int l) { return l == 1 ? OFF_W1 : OFF_W2 + (l - 2) * LAYER_STRIDE; }
+__host__ __device__ constexpr int off_b(int l) { return l == 1 ? OFF_B1 : off_w(l) + FM * FM * 9; }
+static_assert(off_b(4) + FM == NPARAMS, "parameter layout");
+
+// LDS layout (floats): three patches' activations of every layer, then split-K partial tiles
+constexpr int S0 = 9, S1 = 7, S2 = 5, S3 = 3;
+constexpr int L_X = 0;                                  // [3][81]
+constexpr int L_A1 = 256;                               // [3][64][49]
+constexpr int L_A2 = L_A1 + 3 * FM * S1 * S1;           // [3][64][25]
+constexpr int L_A3 = L_A2 + 3 * FM * S2 * S2;           // [3][64][9]
+constexpr int L_A4 = L_A3 + 3 * FM * S3 * S3;           // [3][64]
+constexpr int L_SPLIT = L_A4 + 3 * FM;                  // [8][16][64] partial tiles
+constexpr int L_TOTAL = L_SPLIT + NW * 16 * 64;
+constexpr size_t STEP_LDS_BYTES = (size_t)L_TOTAL * sizeof(float);
+
+// ---- patch sampler: make_patch (main.lua:603-619) + OpenCV 2.4 cvWarpAffine, INTER_CUBIC, constant 0 border ----------
+struct Affine { double m[6]; };
+
+// mul32 (main.lua:603-605), in doubles like Lua
+__device__ inline Affine mul32(const double a[6], const Affine &b)
+{
+	Affine r;
+	r.m[0] = a[0] * b.m[0] + a[1] * b.m[3];
+	r.m[1] = a[0] * b.m[1] + a[1] * b.m[4];
+	r.m[2] = a[0] * b.m[2] + a[1] * b.m[5] + a[2];
+	r.m[3] = a[3] * b.m[0] + a[4] * b.m[3];
+	r.m[4] = a[3] * b.m[1] + a[4] * b.m[4];
+	r.m[5] = a[3] * b.m[2] + a[4] * b.m[5] + a[5];
+	return r;
+}
+
+// interpolateCubic (OpenCV imgproc), A = -0.75, in float
+__device__ inline void cubic_coeffs(float x, float c[4])
+{
+	const float A = -0.75f;
+	c[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
+	c[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
+	c[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
+	c[3] = 1.f - c[0] - c[1] - c[2];
+}
+
+// One output pixel (dx, dy) of a 9 x 9 patch of image `src` (H x W) warped by make_patch's matrix for
+// (row, col, scale, phi, trans, hshear), then * contrast + brightness.
+__device__ float sample_pixel(const float *__restrict__ src, int H, int W, double row, double col, const float *p, int dx, int dy)
+{
+	// p: scale_x scale_y phi trans_x trans_y hshear brightness contrast
+	Affine m = {{1.0, 0.0, -col, 0.0, 1.0, -row}};
+	{ const double t[6] = {1, 0, (double)p[3], 0, 1, (double)p[4]}; m = mul32(t, m); }
+	{ const double t[6] = {(double)p[0], 0, 0, 0, (double)p[1], 0}; m = mul32(t, m); }
+	{
+		const double c = cos((double)p[2]), s = sin((double)p[2]);
+		const double t[6] = {c, s, 0, -s, c, 0};
+		m = mul32(t, m);
+	}
+	{ const double t[6] = {1, (double)p[5], 0, 0, 1, 0}; m = mul32(t, m); }
+	{ const double t[6] = {1, 0, (WS - 1) / 2.0, 0, 1, (WS - 1) / 2.0}; m = mul32(t, m); }
+	double M[6];
+	for (int i = 0; i < 6; ++i) M[i] = (double)(float)m.m[i];   // torch.FloatTensor(m), then OpenCV's convertTo(CV_64F)
+	// warpAffine without WARP_INVERSE_MAP inverts the matrix
+	double D = M[0] * M[4] - M[1] * M[3];
+	D = D != 0 ? 1. / D : 0.;
+	const double A11 = M[4] * D, A22 = M[0] * D;
+	M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
+	const double b1 = -M[0] * M[2] - M[1] * M[5];
+	const double b2 = -M[3] * M[2] - M[4] * M[5];
+	M[2] = b1; M[5] = b2;
+	// fixed point: AB_BITS = 10, INTER_BITS = 5, round_delta = 16
+	const int adelta = (int)rint(M[0] * dx * 1024.0), bdelta = (int)rint(M[3] * dx * 1024.0);
+	const int X0 = (int)rint((M[1] * dy + M[2]) * 1024.0) + 16;
+	const int Y0 = (int)rint((M[4] * dy + M[5]) * 1024.0) + 16;
+	const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
+	const int sx = (X >> 5) - 1, sy = (Y >> 5) - 1;
+	float wx[4], wy[4];
+	cubic_coeffs((float)(X & 31) * (1.f / 32), wx);
+	cubic_coeffs((float)(Y & 31) * (1.f / 32), wy);
+	float sum = 0.f;
+	if ((unsigned)sx < (unsigned)(W - 3) && (unsigned)sy < (unsigned)(H - 3)) {
+		const float *S = src + (int64_t)sy * W + sx;
+		for (int i = 0; i < 4; ++i, S += W) {
+			const float r = S[0] * (wy[i] * wx[0]) + S[1] * (wy[i] * wx[1]) + S[2] * (wy[i] * wx[2]) + S[3] * (wy[i] * wx[3]);
+			sum = i == 0 ? r : sum + r;
+		}
+	} else if (sx >= W || sx + 4 <= 0 || sy >= H || sy + 4 <= 0) {
+		sum = 0.f;
+	} else {
+		for (int i = 0; i < 4; ++i) {
+			const int yi = sy + i;
+			if (yi < 0 || yi >= H) continue;
+			for (int j = 0; j < 4; ++j) {
+				const int xj = sx + j;
+				if (xj >= 0 && xj < W) sum += src[(int64_t)yi * W + xj] * (wy[i] * wx[j]);
+			}
+		}
+	}
+	return sum * p[7] + p[6];   // dst:mul(contrast):add(brightness)
+}
+
+// Pixel t (0 .. 3*81-1) of pair `pair`'s three patches.  Rows outside nnz or images outside x0 read 0.
+__device__ float sample_pair_pixel(const float *__restrict__ x0, const float *__restrict__ x1, int n_img, int H, int W,
+                                   const float *__restrict__ nnz, int64_t n_nnz, int row, const float *__restrict__ prm, int t)
+{
+	const int patch = t / (WS * WS), pix = t - patch * WS * WS;
+	if (row < 0 || row >= n_nnz) return 0.f;
+	const float *z = nnz + (int64_t)row * 4;
+	const int img = (int)z[0];
+	if (img < 1 || img > n_img) return 0.f;
+	const double dim3 = z[1], dim4 = z[2], d = z[3];
+	float p[8];
+	double col;
+	if (patch == 0) {
+		for (int k = 0; k < 8; ++k) p[k] = prm[2 + k];
+		col = dim4;
+	} else {
+		for (int k = 0; k < 8; ++k) p[k] = prm[10 + k];
+		col = dim4 - d + (double)prm[patch == 1 ? 0 : 1];
+	}
+	const float *src = (patch == 0 ? x0 : x1) + (int64_t)(img - 1) * H * W;
+	return sample_pixel(src, H, W, dim3, col, p, pix % WS, pix / WS);
+}
+
+__global__ void __launch_bounds__(256) train_sample_kernel(const float *__restrict__ x0, const float *__restrict__ x1, int n_img, int H, int W,
+                                                           const float *__restrict__ nnz, int64_t n_nnz, const int32_t *__restrict__ rows,
+                                                           const float *__restrict__ prm, float *__restrict__ out)
+{
+	const int pair = blockIdx.x, t = threadIdx.x;
+	if (t < 3 * WS * WS)
+		out[(int64_t)pair * 3 * WS * WS + t] = sample_pair_pixel(x0, x1, n_img, H, W, nnz, n_nnz, rows[pair], prm + (int64_t)pair * NPRM, t);
+}
+
+// ---- block GEMM on the matrix cores --------------------------------------------------------------------------------
+// Tiles of 32 x 32 over (M = 64) x N; a lane holds A[row lane&31][k = lane>>5] and B[k = lane>>5][col lane&31] and its
+// result registers r are rows (r&3) + 8*(r>>2) + 4*(lane>>5) of column lane&31.  KS > 1 splits the K steps into KS
+// slices over the waves; the partial tiles meet in LDS and are added in slice order.
+// mac(acc, i, j, h, s0, s1): run K steps [s0, s1) for output row i / column j on lane half h.
+// out(row, col, v): the epilogue of one element.
+template <int KS, class Mac, class Out>
+__device__ __forceinline__ void block_gemm(int N, int ksteps, float *split, Mac mac, Out out)
+{
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
+	const int ntile = 2 * ((N + 31) / 32);
+	for (int task = wave; task < ntile * KS; task += NW) {
+		const int tile = task / KS, ks = task - tile * KS;
+		const int m0 = (tile & 1) * 32, n0 = (tile >> 1) * 32;
+		floatx16 acc;
+		for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+		mac(acc, m0 + (lane & 31), n0 + (lane & 31), h, ksteps * ks / KS, ksteps * (ks + 1) / KS);
+		if (KS == 1) {
+			const int col = n0 + (lane & 31);
+			if (col < N)
+				for (int r = 0; r < 16; ++r) out(m0 + (r & 3) + 8 * (r >> 2) + 4 * h, col, acc[r]);
+		} else {
+			for (int r = 0; r < 16; ++r) split[(task * 16 + r) * 64 + lane] = acc[r];
+		}
+	}
+	if (KS > 1) {
+		__syncthreads();
+		for (int e = threadIdx.x; e < ntile * 16 * 64; e += NT) {
+			const int tile = e >> 10, r = (e >> 6) & 15, l = e & 63;
+			const int m0 = (tile & 1) * 32, n0 = (tile >> 1) * 32, col = n0 + (l & 31);
+			float v = split[((tile * KS) * 16 + r) * 64 + l];
+			for (int ks = 1; ks < KS; ++ks) v += split[((tile * KS + ks) * 16 + r) * 64 + l];
+			if (col < N) out(m0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), col, v);
+		}
+	}
+}
+
+__device__ __forceinline__ floatx16 mfma(float a, float b, floatx16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+
+// forward of layer with CIN input maps of SI x SI per patch into FM maps of (SI-2)^2: out = b + W * in (+ ReLU)
+template <int CIN, int SI, int KS>
+__device__ void conv_forward(const float *__restrict__ w, const float *__restrict__ bias, const float *in, float *out, bool relu, float *split)
+{
+	constexpr int SO = SI - 2, PO = SO * SO, PI = SI * SI, N = 3 * PO;
+	auto mac = [&](floatx16 &acc, int i, int j, int h, int s0, int s1) {
+		const int jc = j < N ? j : N - 1;
+		const int patch = jc / PO, pix = jc - patch * PO, py = pix / SO, px = pix - py * SO;
+		const float *pb = in + patch * CIN * PI + py * SI + px;
+		if constexpr (CIN == 1) {
+			for (int s = s0; s < s1; ++s) {
+				const int tap = 2 * s + h;
+				const float a = tap < 9 ? w[i * 9 + tap] : 0.f;
+				const float b = tap < 9 ? pb[(tap / 3) * SI + tap % 3] : 0.f;
+				acc = mfma(a, b, acc);
+			}
+		} else {
+			const float *pa = w + i * CIN * 9 + h * 9 + s0 * 18;
+			pb += h * PI + s0 * 2 * PI;
+			for (int s = s0; s < s1; ++s, pa += 18, pb += 2 * PI) {
+				float a[9];
+#pragma unroll
+				for (int t = 0; t < 9; ++t) a[t] = pa[t];
+#pragma unroll
+				for (int t = 0; t < 9; ++t) acc = mfma(a[t], pb[(t / 3) * SI + t % 3], acc);
+			}
+		}
+	};
+	auto put = [&](int co, int j, float v) {
+		const int patch = j / PO, pix = j - patch * PO;
+		v = v + bias[co];
+		out[(patch * FM + co) * PO + pix] = relu ? fmaxf(v, 0.f) : v;
+	};
+	block_gemm<KS>(N, CIN == 1 ? 5 : CIN / 2, split, mac, put);
+}
+
+// weight and bias gradients of a layer: dW[co, ci, tap] = sum_p g[co, p] in[ci, p + tap] into slab (no atomics)
+template <int CIN, int SI>
+__device__ void conv_weight_grad(const float *g, const float *in, float *__restrict__ dw, float *__restrict__ db, float *split)
+{
+	constexpr int SO = SI - 2, PO = SO * SO, PI = SI * SI, P = 3 * PO, KN = CIN * 9;
+	auto mac = [&](floatx16 &acc, int i, int j, int h, int s0, int s1) {
+		const int jc = j < KN ? j : KN - 1;
+		const int ci = jc / 9, tap = jc - ci * 9;
+		const float *pb = in + ci * PI + (tap / 3) * SI + tap % 3;
+		const float *pa = g + i * PO;
+		for (int s = s0; s < s1; ++s) {
+			const int p = 2 * s + h;
+			const int pc = p < P ? p : P - 1;
+			const int patch = pc / PO, pix = pc - patch * PO, py = pix / SO, px = pix - py * SO;
+			const float a = p < P ? pa[patch * FM * PO + pix] : 0.f;
+			const float b = p < P ? pb[patch * CIN * PI + py * SI + px] : 0.f;
+			acc = mfma(a, b, acc);
+		}
+	};
+	auto put = [&](int co, int j, float v) { dw[co * KN + j] = v; };
+	block_gemm<1>(KN, (P + 1) / 2, split, mac, put);
+	if (threadIdx.x < FM) {
+		const int co = threadIdx.x;
+		float s = 0.f;
+		for (int patch = 0; patch < 3; ++patch)
+			for (int pix = 0; pix < PO; ++pix) s += g[(patch * FM + co) * PO + pix];
+		db[co] = s;
+	}
+}
+
+// data gradient of a layer into its input activations, in place, masked by their ReLU: in[ci, q] = in > 0 ? dX : 0
+template <int SI, int KS>
+__device__ void conv_data_grad(const float *__restrict__ w, const float *g, float *in, float *split)
+{
+	constexpr int SO = SI - 2, PO = SO * SO, PI = SI * SI, N = 3 * PI;
+	auto mac = [&](floatx16 &acc, int i, int j, int h, int s0, int s1) {
+		const int jc = j < N ? j : N - 1;
+		const int patch = jc / PI, q = jc - patch * PI, qy = q / SI, qx = q - qy * SI;
+		bool ok[9];
+#pragma unroll
+		for (int t = 0; t < 9; ++t) {
+			const int y = qy - t / 3, x = qx - t % 3;
+			ok[t] = y >= 0 && y < SO && x >= 0 && x < SO;
+		}
+		// g[patch][co = 2s + h][qy - ky][qx - kx]; out-of-range taps read 0 (the offsets are only formed where valid)
+		const int gb = patch * FM * PO + h * PO + qy * SO + qx;
+		const float *pa = w + h * FM * 9 + i * 9 + s0 * 2 * FM * 9;
+		for (int s = s0; s < s1; ++s, pa += 2 * FM * 9) {
+			float a[9];
+#pragma unroll
+			for (int t = 0; t < 9; ++t) a[t] = pa[t];
+			const int base = gb + s * 2 * PO;
+#pragma unroll
+			for (int t = 0; t < 9; ++t) acc = mfma(a[t], ok[t] ? g[base - (t / 3) * SO - t % 3] : 0.f, acc);
+		}
+	};
+	auto put = [&](int ci, int j, float v) {
+		const int patch = j / PI, q = j - patch * PI;
+		float *p = in + (patch * FM + ci) * PI + q;
+		*p = *p > 0.f ? v : 0.f;
+	};
+	block_gemm<KS>(N, FM / 2, split, mac, put);
+}
+
+__device__ __forceinline__ float wave_sum(float v)
+{
+	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+	return v;
+}
+
+// Kernel (a): one workgroup per pair.  SAMPLE: the patches come from the images (rows[pair] of nnz, prm of the pair);
+// otherwise from patches (n_pairs, 3, 9, 9).  Writes the pair's gradients to slab[pair] and its loss to losses[pair].
+template <bool SAMPLE>
+__global__ void __launch_bounds__(NT) train_step_kernel(const float *__restrict__ patches,
+                                                        const float *__restrict__ x0, const float *__restrict__ x1, int n_img, int H, int W,
+                                                        const float *__restrict__ nnz, int64_t n_nnz, const int32_t *__restrict__ rows,
+                                                        const float *__restrict__ prm, const float *__restrict__ params,
+                                                        float margin, int pow, float inv_pairs, float *__restrict__ slab, float *__restrict__ losses)
+{
+	extern __shared__ __attribute__((aligned(16))) float lds[];
+	const int pair = blockIdx.x, t = threadIdx.x;
+	float *X = lds + L_X, *A1 = lds + L_A1, *A2 = lds + L_A2, *A3 = lds + L_A3, *A4 = lds + L_A4, *split = lds + L_SPLIT;
+	if (t < 3 * WS * WS) {
+		if (SAMPLE)
+			X[t] = sample_pair_pixel(x0, x1, n_img, H, W, nnz, n_nnz, rows[pair], prm + (int64_t)pair * NPRM, t);
+		else
+			X[t] = patches[(int64_t)pair * 3 * WS * WS + t];
+	}
+	__syncthreads();
+	conv_forward<1, S0, 1>(params + off_w(1), params + off_b(1), X, A1, true, split);
+	__syncthreads();
+	conv_forward<FM, S1, 1>(params + off_w(2), params + off_b(2), A1, A2, true, split);
+	__syncthreads();
+	conv_forward<FM, S2, 4>(params + off_w(3), params + off_b(3), A2, A3, true, split);
+	__syncthreads();
+	conv_forward<FM, S3, 4>(params + off_w(4), params + off_b(4), A3, A4, false, split);
+	__syncthreads();
+	// Normalize2 (adcensus.cu:1284-1333), StereoJoin1, Margin2 (adcensus.cu:1379-1451) and their backward passes
+	if (t < 64) {
+		const int c = t;
+		float x[3], n[3], y[3];
+		for (int p = 0; p < 3; ++p) {
+			x[p] = A4[p * FM + c];
+			n[p] = wave_sum(x[p] * x[p]) + 1e-5f;
+			y[p] = x[p] / sqrtf(n[p]);
+		}
+		const float pos = wave_sum(y[0] * y[1]), neg = wave_sum(y[0] * y[2]);
+		const float f = neg - pos + margin;
+		float loss, gp, gn;
+		if (pow == 1) {
+			loss = fmaxf(0.f, f);
+			gp = -1.f * (f > 0);
+			gn = (float)(f > 0);
+		} else {
+			const float d = fmaxf(0.f, f);
+			loss = d * d * 0.5f;
+			gp = -f * (f > 0);
+			gn = f * (f > 0);
+		}
+		gp *= inv_pairs;
+		gn *= inv_pairs;
+		// StereoJoin1 backward; the left patch gets both pairs' contributions
+		float go[3] = {y[1] * gp + y[2] * gn, y[0] * gp, y[0] * gn};
+		for (int p = 0; p < 3; ++p) {
+			const float denom = powf(n[p], 1.5f);
+			const float dot = wave_sum(x[p] * go[p]);
+			const float others = dot - x[p] * go[p];
+			A4[p * FM + c] = (n[p] - x[p] * x[p]) / denom * go[p] - others * x[p] / denom;
+		}
+		if (c == 0) losses[pair] = loss;
+	}
+	__syncthreads();
+	float *g = slab + (int64_t)pair * NPARAMS;
+	conv_weight_grad<FM, S3>(A4, A3, g + off_w(4), g + off_b(4), split);
+	__syncthreads();
+	conv_data_grad<S3, 4>(params + off_w(4), A4, A3, split);
+	__syncthreads();
+	conv_weight_grad<FM, S2>(A3, A2, g + off_w(3), g + off_b(3), split);
+	__syncthreads();
+	conv_data_grad<S2, 1>(params + off_w(3), A3, A2, split);
+	__syncthreads();
+	conv_weight_grad<FM, S1>(A2, A1, g + off_w(2), g + off_b(2), split);
+	__syncthreads();
+	conv_data_grad<S1, 1>(params + off_w(2), A2, A1, split);
+	__syncthreads();
+	conv_weight_grad<1, S0>(A1, X, g + off_w(1), g + off_b(1), split);
+}
+
+// Kernel (b): g = sum over pairs in order; v = mom * v - lr * g; w += v.  Block 0 also writes the mean loss.
+__global__ void __launch_bounds__(256) train_sgd_kernel(const float *__restrict__ slab, const float *__restrict__ pair_losses, int n_pairs,
+                                                        float *__restrict__ params, float *__restrict__ moms, float lr, float mom,
+                                                        float *__restrict__ loss_out)
+{
+	const int j = blockIdx.x * blockDim.x + threadIdx.x;
+	if (j < NPARAMS) {
+		float g = 0.f;
+		for (int p = 0; p < n_pairs; ++p) g += slab[(int64_t)p * NPARAMS + j];
+		const float v = moms[j] * mom - lr * g;
+		moms[j] = v;
+		params[j] = params[j] + v;
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		float s = 0.f;
+		for (int p = 0; p < n_pairs; ++p) s += pair_losses[p];
+		*loss_out = s / (float)n_pairs;
+	}
+}
+
+static size_t slab_bytes(int n_pairs) { return (size_t)n_pairs * NPARAMS * sizeof(float); }
+
+static int prepare_step_kernels()
+{
+	static int rc = -1;
+	if (rc >= 0) return rc;
+	hipError_t e = hipFuncSetAttribute((const void *)train_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_LDS_BYTES);
+	if (e == hipSuccess)
+		e = hipFuncSetAttribute((const void *)train_step_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STEP_LDS_BYTES);
+	if (e != hipSuccess) {
+		set_error("train: hipFuncSetAttribute(%zu bytes of LDS): %s", STEP_LDS_BYTES, hipGetErrorString(e));
+		return (int)e;
+	}
+	rc = 0;
+	return rc;
+}
+
+static int check_step_args(int n_pairs, const float *params, const float *moms, float margin, int pow, void *ws, size_t ws_bytes)
+{
+	MC_REQUIRE(n_pairs >= 1 && n_pairs <= MC_TRAIN_MAX_PAIRS, "train: n_pairs %d outside [1, %d]", n_pairs, MC_TRAIN_MAX_PAIRS);
+	MC_REQUIRE(params && moms, "train: null params / momenta");
+	MC_REQUIRE(pow == 1 || pow == 2, "train: pow %d (Margin2 has pow 1 and 2, adcensus.cu:1427-1447)", pow);
+	MC_REQUIRE(isfinite(margin), "train: margin not finite");
+	MC_REQUIRE(ws && ws_bytes >= mc_train_workspace_bytes(n_pairs), "train: workspace of %zu bytes, %zu needed", ws_bytes,
+	           mc_train_workspace_bytes(n_pairs));
+	return 0;
+}
+
+static int check_image_args(const float *x0, const float *x1, int n_img, int H, int W, const float *nnz, int64_t n_nnz)
+{
+	MC_REQUIRE(x0 && x1 && nnz, "train: null image / nnz pointer");
+	MC_REQUIRE(n_img >= 1 && H >= 4 && W >= 4 && (int64_t)n_img * H * W < ((int64_t)1 << 40), "train: bad image dims %d x %d x %d", n_img, H, W);
+	MC_REQUIRE(H < 32768 && W < 32768, "train: images of %d x %d exceed the warp's 16-bit coordinates", H, W);
+	MC_REQUIRE(n_nnz >= 1, "train: empty nnz");
+	return 0;
+}
+
+}  // namespace mc
+
+using namespace mc;
+
+extern "C" {
+
+int mc_train_version(void) { return MC_TRAIN_ABI_VERSION; }
+
+const char *mc_train_last_error(void) { return g_train_err; }
+
+size_t mc_train_workspace_bytes(int n_pairs)
+{
+	if (n_pairs < 1 || n_pairs > MC_TRAIN_MAX_PAIRS) return 0;
+	return slab_bytes(n_pairs) + (size_t)n_pairs * sizeof(float);
+}
+
+int mc_train_sample(const float *x0, const float *x1, int n_img, int H, int W, const float *nnz, int64_t n_nnz, const int32_t *rows,
+                    const float *prm, int n_pairs, float *out, void *stream)
+{
+	if (int rc = check_image_args(x0, x1, n_img, H, W, nnz, n_nnz)) return rc;
+	MC_REQUIRE(n_pairs >= 1 && n_pairs <= (1 << 24), "train_sample: n_pairs %d", n_pairs);
+	MC_REQUIRE(rows && prm && out, "train_sample: null pointer");
+	train_sample_kernel<<<n_pairs, 256, 0, as_stream(stream)>>>(x0, x1, n_img, H, W, nnz, n_nnz, rows, prm, out);
+	return check_launch("train_sample");
+}
+
+static int enqueue_step(const float *patches, const float *x0, const float *x1, int n_img, int H, int W, const float *nnz, int64_t n_nnz,
+                        const int32_t *rows, const float *prm, int n_pairs, float *params, float *moms, float lr, float mom, float margin,
+                        int pow, float *loss_out, void *ws, hipStream_t st)
+{
+	float *slab = (float *)ws;
+	float *pair_losses = slab + (size_t)n_pairs * NPARAMS;
+	if (patches)
+		train_step_kernel<false><<<n_pairs, NT, STEP_LDS_BYTES, st>>>(patches, x0, x1, n_img, H, W, nnz, n_nnz, rows, prm, params, margin,
+		                                                               pow, 1.f / (float)n_pairs, slab, pair_losses);
+	else
+		train_step_kernel<true><<<n_pairs, NT, STEP_LDS_BYTES, st>>>(patches, x0, x1, n_img, H, W, nnz, n_nnz, rows, prm, params, margin,
+		                                                              pow, 1.f / (float)n_pairs, slab, pair_losses);
+	if (int rc = check_launch("train_step")) return rc;
+	train_sgd_kernel<<<cdiv(NPARAMS, 256), 256, 0, st>>>(slab, pair_losses, n_pairs, params, moms, lr, mom, loss_out);
+	return check_launch("train_sgd");
+}
+
+int mc_train_step_batch(const float *patches, int n_pairs, float *params, float *moms, float lr, float mom, float margin, int pow,
+                        float *loss_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+	if (int rc = check_step_args(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
+	MC_REQUIRE(patches && loss_out, "train_step_batch: null pointer");
+	if (int rc = prepare_step_kernels()) return rc;
+	return enqueue_step(patches, nullptr, nullptr, 0, 0, 0, nullptr, 0, nullptr, nullptr, n_pairs, params, moms, lr, mom, margin, pow,
+	                    loss_out, workspace, as_stream(stream));
+}
+
+int mc_train_run(const float *x0, const float *x1, int n_img, int H, int W, const float *nnz, int64_t n_nnz, const int32_t *perm,
+                 int64_t n_perm, int64_t t0, int n_steps, int n_pairs, const float *prm, float *params, float *moms, float lr, float mom,
+                 float margin, int pow, float *losses, void *workspace, size_t workspace_bytes, void *stream)
+{
+	if (int rc = check_image_args(x0, x1, n_img, H, W, nnz, n_nnz)) return rc;
+	if (int rc = check_step_args(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
+	MC_REQUIRE(perm && prm && losses, "train_run: null pointer");
+	MC_REQUIRE(n_steps >= 0, "train_run: n_steps %d", n_steps);
+	MC_REQUIRE(t0 >= 0 && t0 + (int64_t)n_steps * n_pairs <= n_perm, "train_run: steps [%lld, %lld) of the permutation exceed its %lld rows",
+	           (long long)t0, (long long)(t0 + (int64_t)n_steps * n_pairs), (long long)n_perm);
+	if (int rc = prepare_step_kernels()) return rc;
+	const hipStream_t st = as_stream(stream);
+	for (int s = 0; s < n_steps; ++s) {
+		const int64_t first = t0 + (int64_t)s * n_pairs;
+		if (int rc = enqueue_step(nullptr, x0, x1, n_img, H, W, nnz, n_nnz, perm + first, prm + (int64_t)s * n_pairs * NPRM, n_pairs, params,
+		                          moms, lr, mom, margin, pow, losses + s, workspace, st))
+			return rc;
+	}
+	return 0;
+}
+
+}  // extern "C"

@@ -14,8 +14,13 @@ volumes from the image pair, main.lua:932-942).
 
 -net_fname: the reference's Torch7 `net_*.t7` (main.lua:892-902; read by `t7.py`), an `.npz` with arrays
 w1,b1,...,w<l1>,b<l1> (w_i: (fm, in, 3, 3); arch slow also fw1,fb1,...), or `random:<seed>` for a seeded random net
-(there is no network access for trained weights).  Hyper-parameter flags (-L1 -tau1 -cbca_i1 -cbca_i2 -pi1 -pi2 -sgm_i
+(`-a train_tr` trains one: see below).  Hyper-parameter flags (-L1 -tau1 -cbca_i1 -cbca_i2 -pi1 -pi2 -sgm_i
 -sgm_q1 -sgm_q2 -alpha1 -tau_so -blur_sigma -blur_t) default to main.lua's per-(dataset, arch) tables.
+
+`-a train_tr | train_all` (kitti | kitti2015, arch fast; main.lua:602-890) train the net on the GPU from `-data_dir`
+(train.py, libmctrain.so) and save net/net_<args>.t7; train_tr then runs test_te.  `-a test_te | test_all`
+(main.lua:1121-1138, 1172-1293) predict the dataset's test (all) pairs with -net_fname and print `runtime err` per pair and
+the mean error.  Training flags keep main.lua's names and defaults; -epochs and -max_steps shorten a run.
 """
 import argparse
 import sys
@@ -52,11 +57,12 @@ def normalize(x):
 
 def parse(argv):
     if len(argv) < 2 or argv[0] not in ("kitti", "kitti2015", "mb") or argv[1] not in ("fast", "slow", "ad", "census"):
-        raise SystemExit("usage: main.py {kitti|kitti2015|mb} {fast|slow|ad|census} -a {predict|time} [flags]  (main.lua:10-13)")
+        raise SystemExit("usage: main.py {kitti|kitti2015|mb} {fast|slow|ad|census} -a {predict|time|train_tr|train_all|test_te|"
+                         "test_all} [flags]  (main.lua:10-13)")
     dataset, arch = argv[0], argv[1]
     t = TABLES[(dataset, arch)]
     ap = argparse.ArgumentParser(prog="main.py %s %s" % (dataset, arch), prefix_chars="-")
-    ap.add_argument("-a", default="predict", choices=["predict", "time"])
+    ap.add_argument("-a", default="predict", choices=["predict", "time"] + list(TRAIN_ACTIONS) + ["submit"])
     ap.add_argument("-net_fname", default="random:42")
     ap.add_argument("-left", default="")
     ap.add_argument("-right", default="")
@@ -69,13 +75,43 @@ def parse(argv):
         ap.add_argument("-" + k, type=float, default=t[k])
     ap.add_argument("-sm_terminate", default="", choices=sorted(SM_TERMINATE), help="main.lua:25")
     ap.add_argument("-sm_skip", default="", choices=sorted(SM_SKIP), help="main.lua:26")
+    add_train_flags(ap, dataset)
     opt = ap.parse_args(argv[2:])
+    if opt.a not in ("predict", "time") and (opt.a not in TRAIN_ACTIONS or dataset not in ("kitti", "kitti2015") or arch != "fast"):
+        raise SystemExit("main.py: -a %s is not supported for %s %s; training and testing cover -a %s for "
+                         "{kitti|kitti2015} fast only (arch slow, Middlebury and -a submit are out of scope)"
+                         % (opt.a, dataset, arch, " | ".join(TRAIN_ACTIONS)))
     prm = dict(t)
     prm["sm_terminate"], prm["sm_skip"] = opt.sm_terminate, opt.sm_skip   # make_params maps the stage names
     for k in ("L1", "cbca_i1", "cbca_i2", "sgm_i", "tau1", "pi1", "pi2", "sgm_q1", "sgm_q2", "alpha1", "tau_so", "blur_sigma",
               "blur_t"):
         prm[k] = getattr(opt, k)
     return dataset, arch, opt, prm
+
+
+TRAIN_ACTIONS = ("train_tr", "train_all", "test_te", "test_all")
+
+# main.lua:33-64 (augmentation, per dataset) and 207-220, 236-248 (arch fast training); the mb values are parsed only
+AUG_DEFAULTS = {
+    "kitti": dict(hflip=0, vflip=0, rotate=7, hscale=0.9, scale=1, trans=0, hshear=0.1, brightness=0.7, contrast=1.3,
+                  d_vtrans=0, d_rotate=0, d_hscale=1, d_hshear=0, d_brightness=0.3, d_contrast=1),
+    "mb": dict(hflip=0, vflip=0, rotate=28, hscale=0.8, scale=0.8, trans=0, hshear=0.1, brightness=1.3, contrast=1.1,
+               d_vtrans=1, d_rotate=3, d_hscale=0.9, d_hshear=0.3, d_brightness=0.7, d_contrast=1.1),
+}
+AUG_DEFAULTS["kitti2015"] = AUG_DEFAULTS["kitti"]
+FAST_TRAIN_DEFAULTS = dict(m=0.2, pow=1, lr=0.002, bs=128, mom=0.9, true1=1, false1=4, false2=10)
+
+
+def add_train_flags(ap, dataset):
+    """The flags of main.lua's training path with its names and defaults (arch fast's values for the optimiser)."""
+    ap.add_argument("-seed", type=int, default=42)
+    for k, v in FAST_TRAIN_DEFAULTS.items():
+        ap.add_argument("-" + k, type=type(v), default=v)
+    for k, v in AUG_DEFAULTS[dataset].items():
+        ap.add_argument("-" + k, type=int if k in ("hflip", "vflip") else float, default=float(v) if k not in ("hflip", "vflip") else v)
+    ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
+    ap.add_argument("-epochs", type=int, default=14, help="main.lua:777 runs 14")
+    ap.add_argument("-max_steps", type=int, default=0, help="stop training after this many steps in all (0: no limit)")
 
 
 FC_SHAPES = {"kitti": (4, 384), "kitti2015": (4, 384), "mb": (3, 384)}  # (l2, nh2), main.lua:76-77, 123-124
@@ -200,6 +236,16 @@ def main(argv=None):
                                         want_volumes=want_volumes)
         raw = raw_volumes_slow(features_slow(x_batch, layers), fc_layers, D, prm["border_n"])
         return stereo_predict_fused(x_batch, prm, D, raw=raw, workspace=workspace, want_volumes=want_volumes)
+    if opt.a in TRAIN_ACTIONS:
+        from . import train
+        if opt.a in ("train_tr", "train_all"):   # main.lua:602-890
+            opt.net_fname = train.train(dataset, arch, opt, list(sys.argv[1:] if argv is None else argv)[2:], dev)
+            if opt.a == "train_all":            # main.lua:884-887 goes on to submit, which is out of scope
+                return 0
+            opt.a = "test_te"
+            layers[:] = device_layers(load_net(opt.net_fname, dataset, arch), dev)
+        train.evaluate(dataset, opt, run, dev)   # main.lua:1121-1138, 1172-1293
+        return 0
     if opt.a == "time":  # main.lua:1140-1167
         if dataset == "mb":
             prm["left_only"] = 1  # outside `-a predict` dataset mb runs direction -1 only (mb_directions, main.lua:953-955)

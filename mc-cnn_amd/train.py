@@ -1,0 +1,288 @@
+"""`main.lua -a train_tr | train_all` for arch fast on kitti / kitti2015 (main.lua:602-890) on the MI355X.
+
+The data (`x0, x1, metadata, tr, te, nnz_tr, nnz_te` of `-data_dir`, main.lua:427-445) is uploaded once; every step --
+sampling the pairs' patches (make_patch + OpenCV's bicubic warpAffine), the forward and backward pass of the Siamese net
+(four valid 3x3 convolutions, ReLU between them, Normalize2, StereoJoin1, the Margin2 hinge) and the momentum-SGD update --
+runs on the GPU in two kernels of libmctrain.so (include/mc_train.h), enqueued chunk by chunk through `mc_train_run` with
+no host round trip inside a chunk.
+
+Randomness: ONE `numpy.random.Generator(-seed)` draws the permutation (once, before the first epoch, main.lua:657; the
+same permutation every epoch) and then, vectorised per chunk of steps, every augmentation parameter of main.lua:790-814
+with the reference's distributions.  Torch's Mersenne-Twister stream is NOT reproduced, so a run does not draw the
+reference's numbers for the same -seed; it is bitwise reproducible for a given -seed on this implementation (gradients
+are reduced in a fixed order, no float atomics).  The initial weights are those of `load_net("random:<seed>")`
+(nn.SpatialConvolution:reset's range).
+
+Not covered: arch slow, Middlebury, -at 1, -subset, -debug, -a submit, multi-GPU.
+"""
+import math
+import os
+import time
+
+import numpy as np
+
+from . import _train_lib as tl
+from .binio import fromfile
+
+CHUNK_STEPS = 256           # steps enqueued per mc_train_run call (one chunk of parameter draws)
+DATA_FILES = ("x0", "x1", "metadata", "tr", "te", "nnz_tr", "nnz_te")
+
+
+def data_dir_of(dataset, opt):
+    return getattr(opt, "data_dir", "") or ("data.kitti" if dataset == "kitti" else "data.kitti2015")
+
+
+def load_data(dataset, opt, names=DATA_FILES):
+    """main.lua:427-445: the arrays of `data.kitti` / `data.kitti2015` (binio.fromfile), as numpy."""
+    d = data_dir_of(dataset, opt)
+    return {k: fromfile(os.path.join(d, k + ".bin")) for k in names}
+
+
+def flat_params(layers):
+    """[(w, b)] of the fast net -> one float32 vector in include/mc_train.h's order (w1 b1 w2 b2 w3 b3 w4 b4)."""
+    out = np.concatenate([np.concatenate([np.asarray(w, np.float32).ravel(), np.asarray(b, np.float32).ravel()]) for w, b in layers])
+    if out.size != tl.NPARAMS:
+        raise ValueError("fast net of %d parameters, libmctrain.so trains %d (l1 4, fm 64, 1 input plane)" % (out.size, tl.NPARAMS))
+    return out
+
+
+def unflat_params(v):
+    v = np.asarray(v, np.float32)
+    layers, o = [], 0
+    for i in range(tl.L1):
+        cin = 1 if i == 0 else tl.FM
+        n = tl.FM * cin * 9
+        layers.append((v[o:o + n].reshape(tl.FM, cin, 3, 3).copy(), v[o + n:o + n + tl.FM].copy()))
+        o += n + tl.FM
+    return layers
+
+
+def n_steps_per_epoch(n, bs):
+    """`for t = 1, n - bs/2, bs/2` (main.lua:787)."""
+    return len(range(1, n - bs // 2 + 1, bs // 2))
+
+
+def draw_params(rng, opt, n_steps, n_pairs):
+    """The augmentation parameters of main.lua:790-814 for n_steps x n_pairs pairs, (n_steps, n_pairs, 18) float32 in the
+    order of include/mc_train.h.  Vectorised numpy draws: the distributions and flags of the reference, not its stream."""
+    sh = (n_steps, n_pairs)
+    u = lambda a, b: rng.uniform(a, b, sh)
+    assert opt.hscale <= 1 and opt.scale <= 1
+    assert opt.contrast >= 1 and opt.d_contrast >= 1
+    d_pos = u(-opt.true1, opt.true1)
+    d_neg = u(opt.false1, opt.false2)
+    d_neg = np.where(rng.uniform(0, 1, sh) < 0.5, -d_neg, d_neg)
+    s = u(opt.scale, 1)
+    sx, sy = s * u(opt.hscale, 1), s
+    if opt.hflip == 1:
+        sx = np.where(rng.uniform(0, 1, sh) < 0.5, -sx, sx)
+    if opt.vflip == 1:
+        sy = np.where(rng.uniform(0, 1, sh) < 0.5, -sy, sy)
+    hshear = u(-opt.hshear, opt.hshear)
+    tx, ty = u(-opt.trans, opt.trans), u(-opt.trans, opt.trans)
+    rot = opt.rotate * math.pi / 180
+    phi = u(-rot, rot)
+    brightness = u(-opt.brightness, opt.brightness)
+    contrast = u(1 / opt.contrast, opt.contrast)
+    sx_ = sx * u(opt.d_hscale, 1)
+    hshear_ = hshear + u(-opt.d_hshear, opt.d_hshear)
+    ty_ = ty + u(-opt.d_vtrans, opt.d_vtrans)
+    drot = opt.d_rotate * math.pi / 180
+    phi_ = phi + u(-drot, drot)
+    brightness_ = brightness + u(-opt.d_brightness, opt.d_brightness)
+    contrast_ = contrast * u(1 / opt.d_contrast, opt.d_contrast)
+    return np.stack([d_pos, d_neg, sx, sy, phi, tx, ty, hshear, brightness, contrast,
+                     sx_, sy, phi_, tx, ty_, hshear_, brightness_, contrast_], axis=-1).astype(np.float32)
+
+
+def _p(t):
+    return t.data_ptr()
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+class Trainer:
+    """Device state of a training run: images, nnz, permutation, parameters, momenta, workspace."""
+
+    def __init__(self, x0, x1, nnz, perm, layers, n_pairs, device):
+        import torch
+        self.lib = tl.load()
+        self.dev = device
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
+        x0, x1 = np.asarray(x0), np.asarray(x1)
+        self.n_img, self.H, self.W = x0.shape[0], x0.shape[-2], x0.shape[-1]
+        self.x0 = f32(x0.reshape(self.n_img, self.H, self.W))
+        self.x1 = f32(x1.reshape(self.n_img, self.H, self.W))
+        self.nnz = f32(np.asarray(nnz).reshape(-1, 4))
+        self.perm = torch.from_numpy(np.ascontiguousarray(perm, np.int32)).to(device)
+        self.params = f32(flat_params(layers))
+        self.moms = torch.zeros_like(self.params)
+        self.n_pairs = n_pairs
+        self.ws_bytes = self.lib.mc_train_workspace_bytes(n_pairs)
+        if self.ws_bytes == 0:
+            raise ValueError("train: %d pairs per batch is outside libmctrain.so's range" % n_pairs)
+        self.ws = torch.empty(self.ws_bytes // 4 + 1, dtype=torch.float32, device=device)
+
+    def run(self, t0, prm, lr, mom, margin, pow_, losses):
+        """mc_train_run: prm (n_steps, n_pairs, 18) on the device; losses (>= n_steps) device float32."""
+        n_steps = prm.shape[0]
+        tl.check(self.lib.mc_train_run(_p(self.x0), _p(self.x1), self.n_img, self.H, self.W, _p(self.nnz), self.nnz.shape[0],
+                                       _p(self.perm), self.perm.shape[0], t0, n_steps, self.n_pairs, _p(prm), _p(self.params),
+                                       _p(self.moms), lr, mom, margin, pow_, _p(losses), self.ws.data_ptr(), self.ws_bytes,
+                                       _stream()), "mc_train_run")
+
+    def layers(self):
+        return unflat_params(self.params.cpu().numpy())
+
+
+def sample(x0, x1, nnz, rows, prm):
+    """mc_train_sample on device tensors: x0, x1 (n_img, H, W), nnz (n, 4), rows (n_pairs,) int32, prm (n_pairs, 18)
+    -> (n_pairs, 3, 9, 9): left, positive, negative patch of each pair."""
+    import torch
+    lib = tl.load()
+    n_img, H, W = x0.shape
+    out = torch.empty((rows.shape[0], 3, tl.WS, tl.WS), dtype=torch.float32, device=x0.device)
+    tl.check(lib.mc_train_sample(_p(x0), _p(x1), n_img, H, W, _p(nnz), nnz.shape[0], _p(rows), _p(prm), rows.shape[0], _p(out),
+                                 _stream()), "mc_train_sample")
+    return out
+
+
+def step_batch(patches, params, moms, lr, mom, margin, pow_, workspace=None):
+    """mc_train_step_batch: one SGD step on patches (n_pairs, 3, 9, 9); params / moms updated in place.  Returns the
+    device scalar of the batch's mean loss."""
+    import torch
+    lib = tl.load()
+    n_pairs = patches.shape[0]
+    need = lib.mc_train_workspace_bytes(n_pairs)
+    if workspace is None:
+        workspace = torch.empty(need // 4 + 1, dtype=torch.float32, device=patches.device)
+    loss = torch.empty(1, dtype=torch.float32, device=patches.device)
+    tl.check(lib.mc_train_step_batch(_p(patches), n_pairs, _p(params), _p(moms), lr, mom, margin, pow_, _p(loss),
+                                     workspace.data_ptr(), workspace.numel() * 4, _stream()), "mc_train_step_batch")
+    return loss
+
+
+def net_fname_of(dataset, arch, argv):
+    """main.lua:344-347, 587-600: net/net_<dataset>_<arch>_<arg>_<arg>....t7."""
+    cmd_str = "_".join([dataset, arch] + [a.replace(os.sep, "_") for a in argv])
+    return os.path.join("net", "net_%s.t7" % cmd_str)
+
+
+def save_net(fname, layers, opt):
+    """torch.save(fname, {clean_net(net_te), opt}, 'ascii') of arch fast (main.lua:587-600): net_te is net_tr with
+    padding 1 and StereoJoin(1) in place of StereoJoin1 (main.lua:739-746)."""
+    from . import t7
+    mods = []
+    for i, (w, b) in enumerate(layers):
+        mods.append(t7.T7Object("cudnn.SpatialConvolution", {
+            "weight": np.ascontiguousarray(w, np.float32), "bias": np.ascontiguousarray(b, np.float32),
+            "nInputPlane": int(w.shape[1]), "nOutputPlane": int(w.shape[0]), "kW": 3, "kH": 3, "dW": 1, "dH": 1,
+            "padW": 1, "padH": 1, "train": False}))
+        if i < len(layers) - 1:
+            mods.append(t7.T7Object("cudnn.ReLU", {"inplace": True, "train": False}))
+    mods.append(t7.T7Object("nn.Normalize2", {"train": False}))
+    mods.append(t7.T7Object("nn.StereoJoin", {"disp_max": 1, "train": False}))
+    net_te = t7.T7Object("nn.Sequential", {"modules": mods, "train": False})
+    opt_t = {k: v for k, v in sorted(vars(opt).items()) if isinstance(v, (bool, int, float, str))}
+    d = os.path.dirname(fname)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    t7.save(fname, [net_te, opt_t])
+    return fname
+
+
+last_run = None   # the latest train() result: {"net_fname", "losses" (per step, float32), "epochs"}
+
+
+def train(dataset, arch, opt, argv, device, data=None):
+    """main.lua:602-890 for -a train_tr / train_all: returns the saved net's file name."""
+    global last_run
+    import torch
+    from .main import load_net
+    if data is None:
+        data = load_data(dataset, opt)
+    nnz = data["nnz_tr"] if opt.a == "train_tr" else np.concatenate([data["nnz_tr"], data["nnz_te"]], 0)
+    nnz = np.asarray(nnz, np.float32).reshape(-1, 4)
+    n_pairs = opt.bs // 2
+    rng = np.random.default_rng(opt.seed)
+    perm = rng.permutation(nnz.shape[0]).astype(np.int32)
+    layers = load_net("random:%d" % opt.seed, dataset, arch)
+    tr = Trainer(data["x0"], data["x1"], nnz, perm, layers, n_pairs, device)
+    steps = n_steps_per_epoch(nnz.shape[0], opt.bs)
+    if steps < 1:
+        raise SystemExit("train: %d training pairs, fewer than a batch of %d" % (nnz.shape[0], n_pairs))
+    budget = opt.max_steps if opt.max_steps > 0 else None
+    lr = opt.lr
+    all_losses = []
+    t_start = time.perf_counter()
+    losses = torch.empty(steps, dtype=torch.float32, device=device)
+    for epoch in range(1, opt.epochs + 1):
+        if budget is not None and budget <= 0:
+            break
+        if epoch == 12:
+            lr = lr / 10
+        n = steps if budget is None else min(steps, budget)
+        for s0 in range(0, n, CHUNK_STEPS):
+            k = min(CHUNK_STEPS, n - s0)
+            prm = torch.from_numpy(draw_params(rng, opt, k, n_pairs)).to(device)
+            tr.run(s0 * n_pairs, prm, lr, opt.mom, opt.m, opt.pow, losses[s0:])
+        ep = losses[:n].cpu().numpy().copy()   # synchronises: the epoch's steps are done
+        all_losses.append(ep)
+        ok = (ep >= 0) & (ep < 100)           # main.lua:861-866
+        for e in ep[~ok]:
+            print("WARNING! err=%f" % e)
+        print(epoch, float(ep[ok].mean()) if ok.any() else float("nan"), lr, time.perf_counter() - t_start)
+        if budget is not None:
+            budget -= n
+    opt.lr = lr
+    fname = save_net(net_fname_of(dataset, arch, argv), tr.layers(), opt)
+    last_run = {"net_fname": fname, "losses": np.concatenate(all_losses) if all_losses else np.zeros(0, np.float32),
+                "epochs": len(all_losses)}
+    return fname
+
+
+def test_examples(opt, data):
+    """main.lua:1121-1138: test_te -> te, test_all -> tr .. te (1-based image indices)."""
+    te = np.asarray(data["te"]).ravel().astype(np.int64)
+    if opt.a == "test_te":
+        return list(te)
+    return list(np.asarray(data["tr"]).ravel().astype(np.int64)) + list(te)
+
+
+def error_rate(pred, actual, err_at):
+    """main.lua:1224-1234: bad pixels (|actual - pred| > err_at) over pixels with actual != 0."""
+    mask = actual != 0
+    bad = (np.abs(actual - pred) > err_at) & mask
+    return float(bad.sum()) / float(mask.sum())
+
+
+def evaluate(dataset, opt, run, device, data=None):
+    """main.lua:1172-1238, 1290-1292 for test_te / test_all: predict each listed pair through `run(x_batch, D)`, print
+    `runtime err` per pair and the mean error.  Returns the mean."""
+    import torch
+    if data is None:
+        data = load_data(dataset, opt, ("x0", "x1", "metadata", "tr", "te", "dispnoc"))
+    x0, x1, meta, dispnoc = data["x0"], data["x1"], np.asarray(data["metadata"]), data["dispnoc"]
+    H, W = x0.shape[-2], x0.shape[-1]
+    err_at = 3
+    errs = []
+    for i in test_examples(opt, data):
+        w = int(meta[i - 1, 1])
+        xb = torch.from_numpy(np.ascontiguousarray(np.stack([x0[i - 1].reshape(1, H, W)[..., :w],
+                                                              x1[i - 1].reshape(1, H, W)[..., :w]]), np.float32)).to(device)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pred = run(xb, opt.disp_max)["disp"]
+        torch.cuda.synchronize()
+        runtime = time.perf_counter() - t0
+        pred = pred.cpu().numpy().reshape(H, w)
+        assert not np.isnan(pred.sum())
+        err = error_rate(pred, np.asarray(dispnoc[i - 1], np.float32).reshape(H, W)[:, :w], err_at)
+        errs.append(err)
+        print(runtime, err)
+    mean = sum(errs) / len(errs)
+    print(mean)
+    return mean

@@ -59,7 +59,7 @@ int sgm_prep(const float *x0, const float *x1, void *maps, int H, int W, float t
 int sgm_contract_violations(const float *vol, int H, int W, int D, unsigned *count, hipStream_t st);
 int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
                const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,
-               float alpha1, float q1, float q2, bool fused, hipStream_t st);
+               float alpha1, float q1, float q2, bool fused, unsigned drop_final, hipStream_t st);
 
 static thread_local char g_err[512] = "";
 
@@ -410,8 +410,11 @@ static int predict_impl(const mc_params *p, const float *x0, const float *x1, co
 			const float *Cv[2] = {cur[0], cur[1]};
 			float *outv[2] = {other(0), other(1)};
 			const bool am = (it == n_sgm - 1) && n_cbca2 == 0;
+			// the right volume's final costs: where no CBCA-2 follows, only right.bin reads them (sub-pixel refinement reads the
+			// left volume, the LR check the arg-min maps that the up sweep writes regardless) -- not stored unless asked for
+			const unsigned drop_final = (am && nvol == 2 && !volR_out) ? 2u : 0u;
 			RUN(sgm_sweeps(Cv, outv, bufC, am ? dispv : nullptr, direction, nvol, H, W, D, ds, maps, p->pi1, p->pi2, p->alpha1,
-			               p->sgm_q1, p->sgm_q2, true, st));
+			               p->sgm_q1, p->sgm_q2, true, drop_final, st));
 			have_disp = am;
 			cur[0] = outv[0]; cur[1] = outv[1];
 		}
@@ -792,7 +795,7 @@ int mc_sgm2(const float *x0, const float *x1, const float *in_hwd, float *out_hw
 	const float *Cv[2] = {in_hwd, in_hwd};
 	float *outv[2] = {out_hwd, out_hwd};
 	const int dirv[2] = {direction, direction};
-	return sgm_sweeps(Cv, outv, nullptr, nullptr, dirv, 1, H, W, D, D, tmp, pi1, pi2, alpha1, sgm_q1, sgm_q2, false, st);
+	return sgm_sweeps(Cv, outv, nullptr, nullptr, dirv, 1, H, W, D, D, tmp, pi1, pi2, alpha1, sgm_q1, sgm_q2, false, 0u, st);
 }
 
 int mc_dhw_to_hwd(const float *in, float *out, int D, int H, int W, void *stream)

@@ -37,6 +37,7 @@ struct SgmPassArgs {
 	float *out[2];        // where this sweep writes
 	float *out2[2];       // DUAL: where the concurrent second direction writes
 	float *disp[2];       // ARGMIN output (H,W), may be null
+	int drop_out[2];      // 1: this pass's stores to out[v] are dropped (nothing reads them; the arg-min is still written)
 	int direction[2];
 	int nvol;
 	int H, W, D, ds;
@@ -178,6 +179,8 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 	const float *__restrict__ Ain2 = A.accin2[v];
 	float *__restrict__ Out = (DUAL && second) ? A.out2[v] : A.out[v];
 	float *__restrict__ Disp = A.disp[v];
+	// a volume whose output nobody reads: its descriptor gets zero records, the range check drops every store (the loop is unchanged)
+	const bool drop = A.drop_out[v];
 
 	// line geometry: pixel of step s is (y0 + s*sy, x0 + s*sx)
 	const int x0s = dirn == 0 ? 0 : (dirn == 1 ? W - 1 : line);
@@ -217,7 +220,7 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 	const __amdgpu_buffer_rsrc_t rC = pixel_rsrc(Cp, (int64_t)minpix * ds, FAR ? 0 : span);
 	const __amdgpu_buffer_rsrc_t rA = pixel_rsrc(NACC >= 1 ? Ain : Cp, (int64_t)minpix * ds, FAR ? 0 : span);
 	const __amdgpu_buffer_rsrc_t rA2 = pixel_rsrc(NACC >= 2 ? Ain2 : Cp, (int64_t)minpix * ds, FAR ? 0 : span);
-	const __amdgpu_buffer_rsrc_t rO = pixel_rsrc(Out, (int64_t)minpix * ds, FAR ? 0 : span);
+	const __amdgpu_buffer_rsrc_t rO = pixel_rsrc(Out, (int64_t)minpix * ds, (FAR || drop) ? 0 : span);
 	const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void *)win, 0, H * Wm + 2 * WBIAS + 64, 0x00020000);
 	const int w0 = y0s * Wm + x0s, dw = sy * Wm + sx;
 	const __amdgpu_buffer_rsrc_t rCls = __builtin_amdgcn_make_buffer_rsrc((void *)cls0, 0, H * W, 0x00020000);
@@ -263,7 +266,7 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 
 	auto store_step = [&](const float (&o)[VPL], int s) {
 		const int64_t pix = FAR ? (int64_t)(y0s + s * sy) * W + (x0s + s * sx) : 0;
-		const __amdgpu_buffer_rsrc_t r = FAR ? pixel_rsrc(Out, pix * ds, run_bytes) : rO;
+		const __amdgpu_buffer_rsrc_t r = FAR ? pixel_rsrc(Out, pix * ds, drop ? 0 : run_bytes) : rO;
 		const unsigned soff = FAR ? 0u : c0v + (unsigned)s * c1v;
 		if (VEC) {
 #pragma unroll
@@ -525,9 +528,11 @@ static void launch_pass(const SgmPassArgs &A, bool vec, hipStream_t st)
 //                  writes (out + out2) + L_2 to out, the up sweep writes (out + L_3)/4 and, if disp[] is
 //                  set, the argmin of the finished pixel.  `out2` is scratch of the same size as out (required),
 //                  ds % 4 == 0 and every volume 16-byte aligned (required: mc_predict's workspace).
+//                  Bit v of drop_final (fused only): the up sweep does not store volume v's final costs -- out[v] is
+//                  left as the down sweep wrote it, the arg-min disp[v] is written as before.
 int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
                const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,
-               float alpha1, float q1, float q2, bool fused, hipStream_t st)
+               float alpha1, float q1, float q2, bool fused, unsigned drop_final, hipStream_t st)
 {
 	// 32-bit pixel indices and line strides in the sweeps (a volume may still exceed 4 GiB: the FAR instances)
 	MC_REQUIRE((int64_t)H * W < ((int64_t)1 << 29) && (int64_t)W * ds * 4 < ((int64_t)1 << 31), "sgm: image %dx%d (pixel stride %d) exceeds the sweeps' 32-bit line arithmetic", H, W, ds);
@@ -541,6 +546,7 @@ int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2
 		A.out2[v] = out2 ? out2[k] : nullptr;
 		A.disp[v] = disp ? disp[k] : nullptr;
 		A.direction[v] = direction[k];
+		A.drop_out[v] = 0;
 	}
 	A.nvol = nvol;
 	A.H = H; A.W = W; A.D = D; A.ds = ds;
@@ -570,6 +576,7 @@ int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2
 		MC_REQUIRE(out2 && vec, "sgm: the fused sweeps need the second direction's scratch and 16-byte aligned volumes with ds %% 4 == 0");
 		launch_pass<0, 0, false, true>(A, vec, st);
 		launch_pass<2, 3, false, false>(A, vec, st);
+		for (int v = 0; v < nvol; ++v) A.drop_out[v] = (drop_final >> v) & 1;
 		if (am) launch_pass<3, 2, true, false>(A, vec, st);
 		else launch_pass<3, 2, false, false>(A, vec, st);
 	}

@@ -37,6 +37,10 @@
  * nnz: (n_nnz, 4) fp32 rows (img 1-based, row, col, disparity), as
  * make_dataset2 writes them (adcensus.cu:1900-1929).  Images: x0 / x1 are
  * (n_img, H, W) fp32, main.lua's X0 / X1 with their single channel dropped.
+ *
+ * Dataset preparation (preprocess_kitti.lua:97-113, since ABI 2): the
+ * ground-truth filters and make_dataset2 for a batch of maps, so that
+ * mc_cnn_amd.preprocess_kitti writes data.kitti / data.kitti2015 on the GPU.
  */
 #ifndef MC_TRAIN_H
 #define MC_TRAIN_H
@@ -49,7 +53,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden */
 
-#define MC_TRAIN_ABI_VERSION 1
+#define MC_TRAIN_ABI_VERSION 2
 #ifndef MC_EINVAL
 #define MC_EINVAL (-22)
 #endif
@@ -59,6 +63,7 @@ extern "C" {
 #define MC_TRAIN_NPRM 18       /* augmentation floats per pair */
 #define MC_TRAIN_NPARAMS 111424 /* 64*9 + 64 + 3 * (64*64*9 + 64) */
 #define MC_TRAIN_MAX_PAIRS 4096
+#define MC_TRAIN_GT_MAX_W 8192 /* widest ground-truth map mc_train_filter_gt takes (one row in LDS) */
 
 int mc_train_version(void);
 const char *mc_train_last_error(void);
@@ -96,6 +101,38 @@ int mc_train_run(const float *x0, const float *x1, int n_img, int H, int W,
                  int n_steps, int n_pairs, const float *prm, float *params, float *moms,
                  float lr, float mom, float margin, int pow, float *losses,
                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* preprocess_kitti.lua:99-101 on n maps disp (n, H, W), in place, with their
+ * left images x0 (n, H, W), in the reference's order (adcensus.cu:1723-1800):
+ *   remove_nonvisible: d >= col                        -> 0;
+ *   remove_occluded:   some i >= 1 with col + i < W and
+ *                      (float)i - d[col + i] < -d[col] -> 0, where d is the
+ *                      row as remove_nonvisible left it (the reference's
+ *                      kernel races on the row; for non-negative maps with
+ *                      exact arithmetic, e.g. PNG16 ground truth, its result
+ *                      is this one);
+ *   remove_white:      x0 == 255                       -> 0.
+ * W <= MC_TRAIN_GT_MAX_W.  n = 0 is a no-op. */
+int mc_train_filter_gt(float *disp, const float *x0, int n, int H, int W, void *stream);
+
+/* Bytes of the workspace of mc_train_nnz_count / _fill for n maps of H rows
+ * (a count and an offset per row); 0 if n * H is out of range. */
+size_t mc_train_nnz_workspace_bytes(int n, int H);
+
+/* make_dataset2 (adcensus.cu:1900-1929), pass 1: counts the pixels with
+ * d > 0.5 of each row of disp (n, H, W), scans the counts into the workspace
+ * and writes the total to count[0] (device int64).  The caller reads the
+ * total to size the output of mc_train_nnz_fill. */
+int mc_train_nnz_count(const float *disp, int n, int H, int W, int64_t *count,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* Pass 2, on the workspace pass 1 left for the same disp and dims: writes the
+ * rows (ids[k], row, col, d) as fp32 (n_nnz, 4) for every d > 0.5 of map k,
+ * in map order, then row-major -- the order in which make_dataset2 appends.
+ * ids (n) are int32 image ids (1-based in preprocess_kitti.lua).  Rows past
+ * n_nnz are not written; nnz is 16-byte aligned. */
+int mc_train_nnz_fill(const float *disp, const int32_t *ids, int n, int H, int W, float *nnz, int64_t n_nnz,
+                      const void *workspace, size_t workspace_bytes, void *stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -8,6 +8,8 @@ The host side here is Python only because the reference's host toolchain
 (LuaJIT + Torch7) is absent from this image; lua/adcensus.lua is the FFI shim
 a Torch7 host would load instead.
 """
+import torch  # noqa: F401  (first: the HIP libraries below then bind to torch's HIP runtime, not to a second one)
+
 from . import _lib  # noqa: F401
 from . import adcensus  # noqa: F401
 from . import batch  # noqa: F401

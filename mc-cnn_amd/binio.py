@@ -18,10 +18,15 @@ def read_bin(path, shape):
 _TYPES = {"float32": "<f4", "int32": "<i4", "int64": "<i8"}
 
 
+def dims(fname):
+    """The extents of the raw array `fname` from its `.dim` sidecar, without reading the array."""
+    return [int(float(line)) for line in open(fname + ".dim").read().split()]
+
+
 def fromfile(fname):
     """main.lua:353-380: a raw array `fname` with sidecars `fname.dim` (one extent per line) and `fname.type`
     (float32 | int32 | int64) -- the dataset format written by preprocess_kitti.lua:118-134 / preprocess_mb.py:99-106."""
-    dim = [int(float(line)) for line in open(fname + ".dim").read().split()]
+    dim = dims(fname)
     if dim == [0]:
         return np.zeros((0,), np.float32)
     t = open(fname + ".type").read().strip()

@@ -20,7 +20,9 @@ w1,b1,...,w<l1>,b<l1> (w_i: (fm, in, 3, 3); arch slow also fw1,fb1,...), or `ran
 `-a train_tr | train_all` (kitti | kitti2015, arch fast; main.lua:602-890) train the net on the GPU from `-data_dir`
 (train.py, libmctrain.so) and save net/net_<args>.t7; train_tr then runs test_te.  `-a test_te | test_all`
 (main.lua:1121-1138, 1172-1293) predict the dataset's test (all) pairs with -net_fname and print `runtime err` per pair and
-the mean error.  Training flags keep main.lua's names and defaults; -epochs and -max_steps shorten a run.
+the mean error.  Training flags keep main.lua's names and defaults; -epochs and -max_steps shorten a run.  `-at 1` trains
+and tests on data.kitti and data.kitti2015 together (main.lua:403-426).  `python -m mc_cnn_amd.preprocess_kitti` writes
+both sets from the KITTI archives (preprocess_kitti.lua).
 """
 import argparse
 import sys
@@ -81,6 +83,8 @@ def parse(argv):
         raise SystemExit("main.py: -a %s is not supported for %s %s; training and testing cover -a %s for "
                          "{kitti|kitti2015} fast only (arch slow, Middlebury and -a submit are out of scope)"
                          % (opt.a, dataset, arch, " | ".join(TRAIN_ACTIONS)))
+    if getattr(opt, "at", 0) == 1 and opt.data_dir:
+        raise SystemExit("main.py: -at 1 reads data.kitti and data.kitti2015 together (main.lua:403-426) and takes no -data_dir")
     prm = dict(t)
     prm["sm_terminate"], prm["sm_skip"] = opt.sm_terminate, opt.sm_skip   # make_params maps the stage names
     for k in ("L1", "cbca_i1", "cbca_i2", "sgm_i", "tau1", "pi1", "pi2", "sgm_q1", "sgm_q2", "alpha1", "tau_so", "blur_sigma",
@@ -110,6 +114,9 @@ def add_train_flags(ap, dataset):
     for k, v in AUG_DEFAULTS[dataset].items():
         ap.add_argument("-" + k, type=int if k in ("hflip", "vflip") else float, default=float(v) if k not in ("hflip", "vflip") else v)
     ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
+    if dataset in ("kitti", "kitti2015"):
+        ap.add_argument("-at", type=int, default=0, choices=(0, 1),
+                        help="1: train on KITTI 2012 and 2015 together (main.lua:72,208,236, 403-426)")
     ap.add_argument("-epochs", type=int, default=14, help="main.lua:777 runs 14")
     ap.add_argument("-max_steps", type=int, default=0, help="stop training after this many steps in all (0: no limit)")
 

@@ -13,7 +13,12 @@ reference's numbers for the same -seed; it is bitwise reproducible for a given -
 are reduced in a fixed order, no float atomics).  The initial weights are those of `load_net("random:<seed>")`
 (nn.SpatialConvolution:reset's range).
 
-Not covered: arch slow, Middlebury, -at 1, -subset, -debug, -a submit, multi-GPU.
+`-at 1` (main.lua:403-426) reads data.kitti and data.kitti2015 together: the 2012 training images, the 2015 training
+images, then the chosen set's test images (for kitti2015 from 2015 image n_tr on: main.lua's X_15[{{200,400}}]); the 2015
+indices and nnz image ids are shifted by 2012's n_tr.  main.lua hard-codes the two n_tr (194, 200); here each is the
+length of its set's dispnoc.bin.  The sets come from `python -m mc_cnn_amd.preprocess_kitti`.
+
+Not covered: arch slow, Middlebury, -subset, -debug, -a submit, multi-GPU.
 """
 import math
 import os
@@ -22,7 +27,7 @@ import time
 import numpy as np
 
 from . import _train_lib as tl
-from .binio import fromfile
+from .binio import dims, fromfile
 
 CHUNK_STEPS = 256           # steps enqueued per mc_train_run call (one chunk of parameter draws)
 DATA_FILES = ("x0", "x1", "metadata", "tr", "te", "nnz_tr", "nnz_te")
@@ -32,10 +37,39 @@ def data_dir_of(dataset, opt):
     return getattr(opt, "data_dir", "") or ("data.kitti" if dataset == "kitti" else "data.kitti2015")
 
 
+AT_DIRS = ("data.kitti", "data.kitti2015")
+
+
 def load_data(dataset, opt, names=DATA_FILES):
-    """main.lua:427-445: the arrays of `data.kitti` / `data.kitti2015` (binio.fromfile), as numpy."""
+    """main.lua:403-445: the arrays of `data.kitti` / `data.kitti2015` (binio.fromfile), as numpy; both sets with -at 1."""
+    if getattr(opt, "at", 0) == 1:
+        return load_data_at(dataset, names)
     d = data_dir_of(dataset, opt)
     return {k: fromfile(os.path.join(d, k + ".bin")) for k in names}
+
+
+def load_data_at(dataset, names=DATA_FILES, dirs=AT_DIRS):
+    """main.lua:403-426 (-at 1): data.kitti and data.kitti2015 combined.  n12 / n15, main.lua's 194 / 200, are the
+    lengths of the sets' dispnoc.bin."""
+    n12, n15 = (dims(os.path.join(d, "dispnoc.bin"))[0] for d in dirs)
+    out = {}
+    for k in names:
+        a12, a15 = (fromfile(os.path.join(d, k + ".bin")) for d in dirs)
+        if k in ("x0", "x1", "metadata"):      # load(): X_12[1..194], X_15[1..200], X_12[195..389] | X_15[200..400]
+            out[k] = np.concatenate([a12[:n12], a15[:n15], a12[n12:] if dataset == "kitti" else a15[n15 - 1:]], 0)
+        elif k == "dispnoc":
+            out[k] = np.concatenate([a12, a15], 0)
+        elif k == "tr":
+            out[k] = np.concatenate([a12, a15 + n12], 0)
+        elif k == "te":
+            out[k] = a12 if dataset == "kitti" else a15 + n12
+        elif k in ("nnz_tr", "nnz_te"):        # load_nnz(): X_15[{{},1}]:add(194)
+            a15 = np.array(a15).reshape(-1, 4)
+            a15[:, 0] += n12
+            out[k] = np.concatenate([np.asarray(a12).reshape(-1, 4), a15], 0)
+        else:
+            raise KeyError("-at 1: no rule to combine %s" % k)
+    return out
 
 
 def flat_params(layers):

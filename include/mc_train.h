@@ -78,7 +78,9 @@ size_t mc_train_workspace_bytes(int n_pairs);
  * CV_INTER_CUBIC + CV_WARP_FILL_OUTLIERS (cv.cpp:19-43): the matrix is
  * inverted, source coordinates are quantised to 1/32 pixel, bicubic weights
  * use A = -0.75, taps outside the image read 0; then dst * contrast +
- * brightness. */
+ * brightness.  A pair whose rows[i] is outside [0, n_nnz) or whose nnz image
+ * id is outside [1, n_img] reads 0 everywhere: its patches are
+ * 0 * contrast + brightness. */
 int mc_train_sample(const float *x0, const float *x1, int n_img, int H, int W,
                     const float *nnz, int64_t n_nnz, const int32_t *rows, const float *prm,
                     int n_pairs, float *out, void *stream);

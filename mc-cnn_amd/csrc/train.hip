@@ -155,25 +155,20 @@ __device__ float sample_pixel(const float *__restrict__ src, int H, int W, doubl
 	return sum * p[7] + p[6];   // dst:mul(contrast):add(brightness)
 }
 
-// Pixel t (0 .. 3*81-1) of pair `pair`'s three patches.  Rows outside nnz or images outside x0 read 0.
+// Pixel t (0 .. 3*81-1) of pair `pair`'s three patches.  Rows outside nnz or images outside x0 read 0: the warp's result is
+// 0, then * contrast + brightness like any patch that lies outside its image.
 __device__ float sample_pair_pixel(const float *__restrict__ x0, const float *__restrict__ x1, int n_img, int H, int W,
                                    const float *__restrict__ nnz, int64_t n_nnz, int row, const float *__restrict__ prm, int t)
 {
 	const int patch = t / (WS * WS), pix = t - patch * WS * WS;
-	if (row < 0 || row >= n_nnz) return 0.f;
+	float p[8];
+	for (int k = 0; k < 8; ++k) p[k] = prm[(patch == 0 ? 2 : 10) + k];
+	if (row < 0 || row >= n_nnz) return 0.f * p[7] + p[6];
 	const float *z = nnz + (int64_t)row * 4;
 	const int img = (int)z[0];
-	if (img < 1 || img > n_img) return 0.f;
+	if (img < 1 || img > n_img) return 0.f * p[7] + p[6];
 	const double dim3 = z[1], dim4 = z[2], d = z[3];
-	float p[8];
-	double col;
-	if (patch == 0) {
-		for (int k = 0; k < 8; ++k) p[k] = prm[2 + k];
-		col = dim4;
-	} else {
-		for (int k = 0; k < 8; ++k) p[k] = prm[10 + k];
-		col = dim4 - d + (double)prm[patch == 1 ? 0 : 1];
-	}
+	const double col = patch == 0 ? dim4 : dim4 - d + (double)prm[patch == 1 ? 0 : 1];
 	const float *src = (patch == 0 ? x0 : x1) + (int64_t)(img - 1) * H * W;
 	return sample_pixel(src, H, W, dim3, col, p, pix % WS, pix / WS);
 }

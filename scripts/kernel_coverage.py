@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Which of libmcadcensus.so's kernels a profiled run launched.
+"""Which of the kernels of libmcadcensus.so and libmctrain.so a profiled run launched.
 
     scripts/kernel_coverage.py KERNEL_STATS_CSV [KERNEL_STATS_CSV ...] [--inventory tests/kernel_inventory.txt]
 
 Reads the kernel_stats.csv files that `rocprofv3 --kernel-trace --stats` writes (e.g. for `pytest tests -m gpu`), normalises the
 kernel names the way tests/kernel_inventory.txt lists them, and prints the inventory kernels the run never launched and the
-library kernels it launched that the inventory does not list.  Only the library's own kernels (namespace mc::) count: torch's and
-the reference's kernels of the same run are ignored.  Exit status 1 if either list is not empty.
+library kernels it launched that the inventory does not list.  Only the two libraries' own kernels (namespace mc::) count, those of
+libmctrain.so (training, dataset preparation) like those of libmcadcensus.so: torch's and the reference's kernels of the same run
+are ignored.  Exit status 1 if either list is not empty.
 
 A name is normalised by dropping `void`, the namespaces, `__device_stub__` (nm's spelling of a kernel's host stub) and the argument
 list: `void mc::sgm_pass_kernel<0, 4, 0, false, true, 8, true, false>(mc::SgmPassArgs)` -> `sgm_pass_kernel<0, 4, 0, false, true,

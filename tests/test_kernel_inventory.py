@@ -1,5 +1,5 @@
-"""CPU: tests/kernel_inventory.txt lists exactly the kernels libmcadcensus.so contains (nm's __device_stub__ symbols, one per
-kernel instantiation the host code can launch), each with the test or tests that launch it.  A new instantiation, or one that
+"""CPU: tests/kernel_inventory.txt lists exactly the kernels libmcadcensus.so and libmctrain.so contain (nm's __device_stub__
+symbols, one per kernel instantiation the host code can launch), each with the test or tests that launch it.  A new instantiation, or one that
 is taken out, has to be entered here together with the test that reaches it (scripts/kernel_coverage.py checks a profiled
 -m gpu run against the same list)."""
 import importlib.util
@@ -37,15 +37,48 @@ def test_normalise():
     assert not kc.is_library_kernel("void at::native::vectorized_elementwise_kernel<4, at::native::FillFunctor<float> >(int)")
 
 
+def built_kernels(mc, kc):
+    """{library file name: its kernels}; both libraries have to exist and hold kernels"""
+    from mc_cnn_amd import _train_lib
+    out = {}
+    for path in (mc._lib.LIB_PATH, _train_lib.LIB_PATH):
+        assert os.path.isfile(path), "%s is not built" % path
+        out[os.path.basename(path)] = library_kernels(path, kc.normalise)
+        assert out[os.path.basename(path)], "no __device_stub__ symbols in %s" % path
+    return out
+
+
+def inventory_errors(inv, built):
+    """(kernels of either library the inventory does not list, entries no library holds)"""
+    union = set().union(*built.values())
+    return sorted(union - set(inv)), sorted(set(inv) - union)
+
+
 def test_inventory_matches_the_library(mc):
     kc = _coverage()
     inv = kc.read_inventory()
-    built = library_kernels(mc._lib.LIB_PATH, kc.normalise)
-    assert built, "no __device_stub__ symbols in %s" % mc._lib.LIB_PATH
-    missing = sorted(built - set(inv))
-    stale = sorted(set(inv) - built)
-    assert not missing and not stale, "kernels of the library not in tests/kernel_inventory.txt: %s; listed there but not built: %s" % (
+    built = built_kernels(mc, kc)
+    assert len(built) == 2 and not set.intersection(*built.values()), "a kernel name in both libraries"
+    missing, stale = inventory_errors(inv, built)
+    assert not missing and not stale, "kernels of the libraries not in tests/kernel_inventory.txt: %s; listed there but not built: %s" % (
         missing, stale)
+
+
+def test_inventory_check_fails_on_a_missing_or_stale_entry_of_either_library(mc):
+    kc = _coverage()
+    inv = kc.read_inventory()
+    built = built_kernels(mc, kc)
+    for lib, names in built.items():
+        victim = sorted(names)[0]
+        less = {k: v for k, v in inv.items() if k != victim}
+        assert inventory_errors(less, built) == ([victim], []), lib
+        grown = {k: set(v) for k, v in built.items()}
+        grown[lib].add("no_such_kernel<1>")
+        assert inventory_errors(inv, grown) == (["no_such_kernel<1>"], []), lib
+        shrunk = {k: set(v) - {victim} for k, v in built.items()}
+        assert inventory_errors(inv, shrunk) == ([], [victim]), lib
+    assert built["libmctrain.so"] == {"train_sample_kernel", "train_step_kernel<true>", "train_step_kernel<false>", "train_sgd_kernel",
+                                      "gt_filter_kernel", "nnz_count_kernel", "nnz_scan_kernel", "nnz_fill_kernel"}
 
 
 def test_every_listed_kernel_names_an_existing_test():

@@ -103,22 +103,60 @@ def sample_pair(x0, x1, nnz_row, prm):
 
 
 # ---- the net and its step in float64 torch autograd ---------------------------------------------------------------------
-def loss_of(layers, patches, margin, pow_):
-    """Margin2(StereoJoin1(Normalize2(net(batch)))) on the reference's 4-patch batch [L, P, L, N] per pair."""
+def tail_parts(h, margin, pow_):
+    """Normalize2 -> StereoJoin1 -> Margin2 on features h (4n, C, 1, 1) [L, P, L, N per pair]: the normalised features,
+    the scores (2n,) [pos, neg per pair] and each pair's loss."""
+    import torch
+    n = h.shape[0] // 4
+    hn = h / torch.sqrt((h * h).sum(1, keepdim=True) + 1e-5)
+    s = (hn[0::2] * hn[1::2]).sum(1).reshape(2 * n)
+    f = s[1::2] - s[0::2] + margin
+    d = torch.clamp(f, min=0)
+    return hn, s, (d if pow_ == 1 else 0.5 * d * d)
+
+
+def features_of(layers, patches, preacts=None):
+    """The net on the reference's 4-patch batch [L, P, L, N] per pair -> (4n, 64, 1, 1).  preacts: a list that receives
+    every layer's pre-activations."""
     import torch
     import torch.nn.functional as F
     n = patches.shape[0]
-    b = torch.stack([patches[:, 0], patches[:, 1], patches[:, 0], patches[:, 2]], 1).reshape(4 * n, 1, WS, WS)
-    h = b
+    h = torch.stack([patches[:, 0], patches[:, 1], patches[:, 0], patches[:, 2]], 1).reshape(4 * n, 1, WS, WS)
     for i, (w, bias) in enumerate(layers):
         h = F.conv2d(h, w, bias)
+        if preacts is not None:
+            preacts.append(h)
         if i < len(layers) - 1:
             h = F.relu(h)
-    h = h / torch.sqrt((h * h).sum(1, keepdim=True) + 1e-5)
-    s = (h[0::2] * h[1::2]).sum(1).reshape(n, 2)
-    f = s[:, 1] - s[:, 0] + margin
-    d = torch.clamp(f, min=0)
-    return (d if pow_ == 1 else 0.5 * d * d).mean()
+    return h
+
+
+def loss_of(layers, patches, margin, pow_):
+    """Margin2(StereoJoin1(Normalize2(net(batch)))) on the reference's 4-patch batch [L, P, L, N] per pair."""
+    return tail_parts(features_of(layers, patches), margin, pow_)[2].mean()
+
+
+def as_f64(layers):
+    import torch
+    return [(torch.tensor(np.asarray(w, np.float64)), torch.tensor(np.asarray(b, np.float64))) for w, b in layers]
+
+
+def hinge_and_fragility(layers, patches, margin, eps=3e-6):
+    """Float64 forward pass of every pair of patches (n, 3, 9, 9): the hinge argument f = neg - pos + margin of each pair,
+    and whether the pair is fragile: some pre-activation of layers 1-3, or f itself, lies within eps of 0, where fp32
+    rounding can put it on the other side and flip a ReLU (or hinge) mask.  Uses the oracle only."""
+    import torch
+    with torch.no_grad():
+        pre = []
+        h = features_of(as_f64(layers), torch.tensor(np.asarray(patches, np.float64)), pre)
+        _, s, _ = tail_parts(h, margin, 1)
+        f = (s[1::2] - s[0::2] + margin).numpy()
+        n = patches.shape[0]
+        small = np.zeros(n, bool)
+        for z in pre[:-1]:
+            small |= (z.abs().reshape(n, -1) < eps).any(1).numpy()
+        small |= np.abs(f) < eps
+    return f, small
 
 
 def sgd_steps(params, patches_list, lr, mom, margin, pow_, fp32_state=False, moms=None):
@@ -152,3 +190,21 @@ def sgd_steps(params, patches_list, lr, mom, margin, pow_, fp32_state=False, mom
                     p.add_(v)
     flat = lambda ts: np.concatenate([t.detach().numpy().ravel() for t in ts])
     return flat(ps), flat(vs), losses
+
+
+def check_per_tensor(got, want, tol, what=""):
+    """Flat w1 b1 .. w4 b4 vectors: each tensor of `got` within tol of that tensor's largest magnitude in `want`, so that no
+    tensor's gradient is partly missing; a tensor that is exactly 0 in `want` has to be exactly 0."""
+    o = 0
+    for i in range(4):
+        for name, n in (("w%d" % (i + 1), 64 * (1 if i == 0 else 64) * 9), ("b%d" % (i + 1), 64)):
+            g, x = got[o:o + n], want[o:o + n]
+            top = np.abs(x).max()
+            if top == 0:
+                assert np.abs(g).max() == 0, "%s %s: float64 says exactly 0" % (what, name)
+            else:
+                err = np.abs(g - x).max() / top
+                print("%s %s: max error %.2e of its largest magnitude %.2e" % (what, name, err, top))
+                assert err <= tol, "%s %s" % (what, name)
+            o += n
+    assert o == got.size == want.size

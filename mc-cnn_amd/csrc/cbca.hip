@@ -4,7 +4,7 @@
 // ascending, inside a row xx ascending, ONE fp32 accumulator, then an IEEE divide by the
 // integer count (adcensus.cu:356-373) -- so that costs, and therefore arg-min disparities,
 // are bit-identical.  No separable / prefix-sum shortcut is taken on this path.
-#include "cbca_common.h"
+#include "launchers.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -77,8 +77,6 @@ __global__ void __launch_bounds__(256) cbca_direct_kernel(const float *__restric
 	}
 	out[id] = sum / (float)cnt;
 }
-
-int cbca_lean_rows(int D, int H, int W, int rb, bool two_pass);   // cbca_lean.hip
 
 int cbca(const float *x0c, const float *x1c, const float *vin, float *vout, int D, int H, int W, int direction, hipStream_t st)
 {
@@ -473,6 +471,48 @@ int cbca_strips(const void *packed, const float *vin, float *vout, int D, int H,
 	if (nt) hipLaunchKernelGGL((cbca_strip_kernel<2, 4, 1, 2, true>), dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, st, A);
 	else hipLaunchKernelGGL((cbca_strip_kernel<2, 4, 1, 2, false>), dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, st, A);
 	return check_launch("cbca_strip");
+}
+
+// shapes the packed-length kernels (strip / tile / lean) take: 32-bit byte offsets inside a plane, and row indices that the tile
+// kernel multiplies with 24-bit multiplies (an image of 2 x 10 000 000 pixels passes the first test only)
+bool packed_dims_ok(int H, int W)
+{
+	return (int64_t)H * W < ((int64_t)1 << 29) - 4096 && H < (1 << 23) - 64 && W < (1 << 23) - 256;
+}
+
+// One aggregation pass over packed arm lengths (cbca_pack).  max_arm = the largest arm that can occur (L1 - 1 where L1 is
+// known, < 0 where it is not: adcensus.cbca).  Arms <= 4: the tile kernel's short-arm instance.  Otherwise the pair's
+// route word (cbca_pack: arm classes actually present, share of pixels with unit arms) decides on the device between the
+// tile kernel's two instances and the strip kernel -- the launches that are not the pair's stand down at their first
+// instruction; nothing is read back by the host.  cfg.lean (mc_predict, from the first pass of a direction on): pairs of the
+// strip kernel's route with arms <= 13 (textures) are served by the lean + list kernels out of the list cbca_classify wrote.
+int cbca_by_arms(const void *packed, const float *vin, float *vout, int D, int H, int W, int direction, int max_arm, hipStream_t st,
+                 const CbcaCfg &cfg)
+{
+	if (max_arm >= 0 && max_arm <= 4) return cbca_tiles(packed, vin, vout, D, H, W, direction, 4, -1, st, cfg);
+	if (cfg.planned) {
+		// mc_predict with a plan area and 5 <= L1 <= 14: ONE candidate per pass beside the texture route's own kernel (round 4: three -- both tile
+		// instances and the strip kernel, ~6 us each to stand down).  Arms <= 4 only: served by the long-arm instance; a texture whose list is
+		// unusable (flat regions next to it): the tile kernel as well, with its plan -- not the strip kernel, whose compaction passes run at the pace of
+		// the largest support
+		int rc = cbca_tiles(packed, vin, vout, D, H, W, direction, 13, CR_PLANNED_TILE13, st, cfg);
+		if (rc || cfg.lean_two_pass) return rc;   // (pairs of passes on a texture: cbca_lean2x, launched by the caller)
+		return cbca_strips(packed, vin, vout, D, H, W, direction, CR_STRIP_IF_LIST, st, cfg);
+	}
+	int rc = cbca_tiles(packed, vin, vout, D, H, W, direction, 4, CR_TILE4, st, cfg);
+	if (rc) return rc;
+	if (max_arm < 0 || max_arm <= 13) {
+		rc = cbca_tiles(packed, vin, vout, D, H, W, direction, 13, CR_TILE13, st, cfg);
+		if (rc) return rc;
+	}
+	if (cfg.lean) {   // textures (route CR_STRIP) out of the pair's list: the lean + list kernels, the strip kernel only if the list is unusable
+		if (!cfg.lean_two_pass) {   // (two passes per launch: cbca_lean2x, launched by the caller for a pair of passes)
+			rc = cbca_lean(packed, cfg.plan, cfg.plan_bytes, vin, vout, D, H, W, direction, CR_STRIP, st, cfg);
+			if (rc) return rc;
+		}
+		return cbca_strips(packed, vin, vout, D, H, W, direction, CR_STRIP_IF_NO_LIST, st, cfg);
+	}
+	return cbca_strips(packed, vin, vout, D, H, W, direction, max_arm > 13 ? CR_STRIP_OR_TILE13 : CR_STRIP, st, cfg);
 }
 
 }  // namespace mc

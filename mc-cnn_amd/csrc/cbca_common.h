@@ -100,9 +100,7 @@ __device__ __forceinline__ bool cbca_gate(const uint32_t *__restrict__ flags, in
 	}
 }
 
-// scratch = [pad | p0 (H*W) | pad | p1 (H*W) | pad | CS_FLAGS flag words], pad = CS_PAD words
-size_t cbca_scratch_bytes(int H, int W);   // cbca.hip
-
+// scratch = [pad | p0 (H*W) | pad | p1 (H*W) | pad | CS_FLAGS flag words], pad = CS_PAD words (cbca_scratch_bytes, cbca.hip)
 struct CbcaScratch { uint32_t *p0, *p1, *flag; };
 static inline CbcaScratch cbca_scratch(const void *scratch, int H, int W)
 {

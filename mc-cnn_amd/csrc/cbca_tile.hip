@@ -27,7 +27,7 @@
 // 1033-1039) and keeps the first pass's work in a PLAN -- per (plane, region, step) the sorted item table and the class
 // counts, per voxel the combined run (2 bytes) and vertical arms (1 byte) as committed to the ring -- which the other passes
 // read a step ahead with the rows (3.5 bytes per voxel of extra traffic for a third of the instructions).
-#include "cbca_common.h"
+#include "launchers.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -911,8 +911,6 @@ static PlanLayout plan_layout(int D, int H, int W)
 	L.total = L.ud + (size_t)D * H * L.wp;
 	return L;
 }
-size_t cbca_lean2x_bytes(int D, int H, int W);   // cbca_lean.hip: what the texture route's two-pass records take of the same area
-int cbca_lean_rows(int D, int H, int W, int rb, bool two_pass);
 size_t cbca_plan_bytes(int D, int H, int W) { return std::max(plan_layout(D, H, W).total, cbca_lean2x_bytes(D, H, W)); }
 
 template <int A, int TW, int TH, int NWAVES, int MODE>

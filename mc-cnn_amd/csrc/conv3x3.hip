@@ -28,7 +28,7 @@
 // reloads the LDS between chunks (two barriers per chunk and tile).
 // The feature maps feeding the pipeline come from cuDNN in the reference, whose algorithm choice is not deterministic
 // (cudnn.benchmark = true, main.lua:330): parity is by tolerance against a plain fp32 convolution, not bit-exact.
-#include "mc_common.h"
+#include "launchers.h"
 #include <type_traits>
 
 namespace mc {

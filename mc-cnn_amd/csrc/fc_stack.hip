@@ -18,7 +18,7 @@
 //   * the last layer (nh2 -> 1) is a dot product per voxel; sigmoid in fp32.
 // The reference's own GEMMs are cuBLAS/cudnn calls whose summation order is not pinned, so parity for this operator is
 // by tolerance (1e-4 on the sigmoid outputs), not bit-exact; tests/test_gpu_fc.py states the bar.
-#include "mc_common.h"
+#include "launchers.h"
 
 namespace mc {
 

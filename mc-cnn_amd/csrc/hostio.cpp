@@ -16,11 +16,8 @@
 #include <vector>
 #include <zlib.h>
 
-#include "../../include/mc_adcensus.h"
+#include "mc_error.h"
 
-namespace mc {
-void set_error(const char *fmt, ...);
-}
 using mc::set_error;
 
 namespace {

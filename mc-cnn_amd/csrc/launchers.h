@@ -1,0 +1,105 @@
+// Every host function of libmcadcensus.so that one unit defines and another calls, declared once.  Every unit includes this,
+// the defining one too, so the compiler sees each declaration next to its definition.  Default arguments live here only.
+#pragma once
+#include "cbca_common.h"
+
+#include <vector>
+
+namespace mc {
+
+// post.hip
+int fill_nan(float *p, int64_t n, hipStream_t st);
+int scale(const float *in, float *out, int64_t n, float s, hipStream_t st);
+int transpose(const float *in, float *out, int64_t R, int64_t Cn, int64_t ldin, int64_t ldout, float s, hipStream_t st, int nt = -1);
+int fix_border(float *vol, int D, int H, int W, int n, int direction, hipStream_t st);
+int argmin_dhw(const float *vol, float *out, int D, int H, int W, int base1, hipStream_t st);
+int outlier_detection(const float *d0, const float *d1, float *outlier, int H, int W, int disp_max, hipStream_t st);
+int interpolate_occlusion(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st);
+int interpolate_mismatch(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st);
+int subpixel(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st);
+int median2d(const float *img, float *out, int H, int W, int k, hipStream_t st);
+int mean2d(const float *img, const float *kernel, float *out, int H, int W, int ks, float alpha2, hipStream_t st);
+int normalize_forward(const float *in, float *norm, float *out, int N, int C, int H, int W, hipStream_t st);
+
+// stereo_join.hip
+int stereo_join_dhw(const float *fL, const float *fR, float *volL, float *volR, int C, int D, int H, int W, hipStream_t st);
+int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, int C, int D, int ds, int H, int W, int n, hipStream_t st);
+int ad_tiled(const float *x0, const float *x1, float *vol, int D, int H, int W, int direction, hipStream_t st);
+size_t census_scratch_bytes(int Cimg, int H, int W);
+int census_sig(const float *x0, const float *x1, float *vol, void *scratch, int Cimg, int D, int H, int W, int direction, hipStream_t st);
+
+// cbca.hip
+int cross(const float *img, float *arms, int H, int W, int L1, float tau1, hipStream_t st);
+int cbca(const float *x0c, const float *x1c, const float *vin, float *vout, int D, int H, int W, int direction, hipStream_t st);
+size_t cbca_scratch_bytes(int H, int W);   // what cbca_scratch() (cbca_common.h) lays out
+int cbca_pack(const float *x0c, const float *x1c, void *scratch, int H, int W, hipStream_t st);
+int cbca_if_overflow(const float *x0c, const float *x1c, const void *packed, const float *vin, float *vout, int D, int H, int W, int direction, hipStream_t st);
+int cbca_strips(const void *packed, const float *vin, float *vout, int D, int H, int W, int direction, int route,
+                hipStream_t st, const CbcaCfg &cfg = CbcaCfg());
+bool packed_dims_ok(int H, int W);
+int cbca_by_arms(const void *packed, const float *vin, float *vout, int D, int H, int W, int direction, int max_arm, hipStream_t st,
+                 const CbcaCfg &cfg = CbcaCfg());
+
+// cbca_tile.hip
+size_t cbca_plan_bytes(int D, int H, int W);
+int cbca_tiles(const void *packed, const float *vin, float *vout, int D, int H, int W, int direction, int arm_class, int route,
+               hipStream_t st, const CbcaCfg &cfg = CbcaCfg());
+
+// cbca_lean.hip
+int cbca_lean_rows(int D, int H, int W, int rb, bool two_pass);
+size_t cbca_lean2x_bytes(int D, int H, int W);   // what the texture route's two-pass records take of the plan area
+bool cbca_lean_fits(int D, int H, int W, size_t plan_bytes, bool two_pass = false, int rb = 0);
+int cbca_classify(const void *packed, void *plan, size_t plan_bytes, int D, int H, int W, int direction, int route, int rb, int cap_limit,
+                  hipStream_t st, bool two_pass = false, float cost_limit = 0);
+int cbca_lean2x(const void *packed, const void *plan, size_t plan_bytes, const float *vin, float *vout, int D, int H, int W, int direction,
+                int route, hipStream_t st, const CbcaCfg &cfg);
+int cbca_lean(const void *packed, const void *plan, size_t plan_bytes, const float *vin, float *vout, int D, int H, int W, int direction,
+              int route, hipStream_t st, const CbcaCfg &cfg);
+
+// conv3x3.hip
+size_t conv3x3_workspace_bytes(int Cin, int Cout);
+int conv3x3(const float *in, const float *w, const float *bias, float *out, int N, int Cin, int Cout, int H, int W, int relu, void *workspace, hipStream_t st);
+
+// fc_stack.hip
+size_t fc_workspace_bytes(int C, int n_hidden, int H, int W);
+int fc_stack(const float *featL, const float *featR, int C, int H, int W, int D, const float *const *weights,
+             const float *const *biases, int n_layers, float *volL, float *volR, void *workspace, hipStream_t st);
+
+// sgm.hip
+size_t sgm_maps_bytes(int H, int W);
+int sgm_prep(const float *x0, const float *x1, void *maps, int H, int W, float tau_so, hipStream_t st);
+int sgm_contract_violations(const float *vol, int H, int W, int D, unsigned *count, hipStream_t st);
+int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
+               const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,
+               float alpha1, float q1, float q2, bool fused, unsigned drop_final, hipStream_t st);
+
+// predict.hip
+static inline int gaussian_ks(double sigma) { return 2 * (int)ceil(sigma * 3) + 1; }   // main.lua:529-530
+void gaussian_fill(double sigma, float *k);
+
+// mc_predict's workspace (make_plan): its size and, for a given base, its areas in the order they lie there
+struct Plan {
+	int Dp;                 // padded pixel stride of the (H,W,Dp) volumes
+	size_t cplan_bytes;     // per direction: the tile kernel's plan (cbca_tile.hip), 0 where it would not be reused
+	size_t total;
+	void *maps, *packed;
+	float *x0c, *x1c, *img[6], *gk;
+	float *bufA[2], *bufB[2], *bufC[2];   // ping-pong per side; bufC: scratch of the SGM's concurrent second direction and of pairs of CBCA passes
+	void *cplan[2];             // null where the direction has none
+};
+Plan make_plan(const mc_params *p, int D, int H, int W, void *base = nullptr);
+
+struct StageTimer {   // mc_predict_timed: an event at every stage boundary
+	bool on = false;
+	hipStream_t st;
+	std::vector<hipEvent_t> ev;
+	std::vector<int> tag;  // stage id the interval ENDING at this event belongs to
+	void mark(int stage);
+	void collect(float out[MC_N_STAGES]);
+};
+int predict_impl(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,
+                 const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
+                 float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out, float *disp_out, hipStream_t st,
+                 StageTimer &tm);
+
+}  // namespace mc

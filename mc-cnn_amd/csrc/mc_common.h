@@ -7,23 +7,14 @@
 #include <stdlib.h>
 
 #include "../../include/mc_adcensus.h"
+#include "mc_error.h"
 
 namespace mc {
 
-// ---- error reporting (mc_last_error) ---------------------------------------
-void set_error(const char *fmt, ...);
-int check_launch(const char *what);  // hipPeekAtLastError -> rc, like checkCudaError (adcensus.cu:31-36)
-
-#define MC_REQUIRE(cond, ...)                 \
-	do {                                      \
-		if (!(cond)) {                        \
-			mc::set_error(__VA_ARGS__);       \
-			return MC_EINVAL;                 \
-		}                                     \
-	} while (0)
-
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline bool dims_ok(int D, int H, int W) { return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H * W < ((int64_t)1 << 40); }
 
 // launch configuration of the cbca strip / tile kernels; the defaults derive everything from the problem size
 struct CbcaCfg {

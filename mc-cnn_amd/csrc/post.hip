@@ -1,6 +1,6 @@
 // H*W-sized disparity kernels and layout helpers (gfx950).
 // Each kernel cites the adcensus.cu kernel whose arithmetic it reproduces.
-#include "mc_common.h"
+#include "launchers.h"
 
 namespace mc {
 

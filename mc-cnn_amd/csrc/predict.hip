@@ -1,0 +1,353 @@
+// The fused stereo_predict pipeline behind mc_predict / mc_predict_timed (main.lua:929-1082): its workspace, the stages that
+// -sm_terminate / -sm_skip leave, and the launches in order.  The extern "C" surface is api.hip.
+#include "launchers.h"
+
+#include <map>
+#include <mutex>
+
+namespace mc {
+
+// gaussian(sigma), main.lua:528-540, double on the host.  Cached per sigma in PINNED host memory (allocated once, never
+// freed), so that the per-call upload into the workspace is a true asynchronous copy that never sees its source disappear.
+void gaussian_fill(double sigma, float *k)
+{
+	const int ks = gaussian_ks(sigma), kr = ks / 2;
+	for (int i = 1; i <= ks; ++i) {
+		for (int j = 1; j <= ks; ++j) {
+			const double y = (i - 1) - kr;
+			const double x = (j - 1) - kr;
+			k[(size_t)(i - 1) * ks + (j - 1)] = (float)exp(-(x * x + y * y) / (2 * sigma * sigma));
+		}
+	}
+}
+struct GaussianK { const float *data; size_t n; };
+static int gaussian_cached(double sigma, GaussianK &out)
+{
+	static std::mutex mu;
+	static std::map<double, GaussianK> cache;
+	std::lock_guard<std::mutex> lk(mu);
+	auto it = cache.find(sigma);
+	if (it != cache.end()) { out = it->second; return 0; }
+	const int ks = gaussian_ks(sigma);
+	float *k = nullptr;
+	const hipError_t e = hipHostMalloc((void **)&k, (size_t)ks * ks * sizeof(float), hipHostMallocDefault);
+	if (e != hipSuccess) {
+		set_error("gaussian: hipHostMalloc: %s", hipGetErrorString(e));
+		return (int)e;
+	}
+	gaussian_fill(sigma, k);
+	out = GaussianK{k, (size_t)ks * ks};
+	cache[sigma] = out;
+	return 0;
+}
+
+// -sm_terminate / -sm_skip (main.lua:956,988-1040) are identical for both directions, so for the three volume stages they
+// reduce to effective iteration counts
+struct StageCounts { int cbca1, sgm, cbca2; bool active_after; };
+static StageCounts stage_counts(const mc_params *p)
+{
+	StageCounts c;
+	bool sm_active = p->sm_terminate != MC_SM_CNN;
+	c.cbca1 = (sm_active && p->sm_skip != MC_SKIP_CBCA) ? p->cbca_i1 : 0;
+	sm_active = sm_active && p->sm_terminate != MC_SM_CBCA1;
+	c.sgm = (sm_active && p->sm_skip != MC_SKIP_SGM) ? p->sgm_i : 0;
+	sm_active = sm_active && p->sm_terminate != MC_SM_SGM;
+	c.cbca2 = (sm_active && p->sm_skip != MC_SKIP_CBCA) ? p->cbca_i2 : 0;
+	sm_active = sm_active && p->sm_terminate != MC_SM_CBCA2;
+	c.active_after = sm_active;
+	return c;
+}
+
+// The one place that lays mc_predict's workspace out: the sizes of its areas, their sum and -- unless base is null -- where each lies.
+Plan make_plan(const mc_params *p, int D, int H, int W, void *base)
+{
+	Plan pl;
+	// pixel stride of the (H,W,ds) volumes: D rounded up to 4 (16-byte runs).  Rounding up to 32 (every run on whole 128-byte
+	// lines) was measured on one box at 370x1226x228 (ds 228 -> 256): the transposes 0.465 -> 0.377 ms, the sweeps 2.016 ->
+	// 2.105 ms (12 % more bytes), StereoJoin unchanged; 6.000 -> 5.998 ms with the aggregation, 2.87 -> 2.97 ms without: not adopted.
+	pl.Dp = (D + 3) / 4 * 4;
+	const size_t HW = (size_t)H * W;
+	const size_t vol = align_up((size_t)pl.Dp * HW * sizeof(float), 256), img = align_up(HW * sizeof(float), 256);
+	const int ks = gaussian_ks(p->blur_sigma);
+	// the tile kernel's bookkeeping is the same in every aggregation pass over the pair and direction: kept from the first pass
+	// on (cbca_plan_bytes: ~3.6 bytes per voxel) -- where a second pass exists to read it (after -sm_skip / -sm_terminate),
+	// and per direction that is computed (left_only without the LR check: the left volume only; a caller who then asks for
+	// right-side outputs gets that direction without a plan)
+	const StageCounts sc = stage_counts(p);
+	pl.cplan_bytes = (sc.cbca1 + sc.cbca2 >= 2 && p->L1 - 1 <= 13) ? align_up(cbca_plan_bytes(D, H, W), 256) : 0;
+	const int nplan = (p->left_only && !p->lr_check) ? 1 : 2;   // directions that get one
+
+	size_t off = 0;
+	auto take = [&](size_t bytes) { off += bytes; return base ? (char *)base + (off - bytes) : nullptr; };
+	pl.maps = take(align_up(sgm_maps_bytes(H, W), 256));
+	pl.x0c = (float *)take(align_up(8 * HW * sizeof(float), 256));
+	pl.x1c = base ? pl.x0c + 4 * HW : nullptr;
+	pl.packed = take(cbca_scratch_bytes(H, W));
+	for (float **buf : {pl.bufA, pl.bufB, pl.bufC})
+		for (int v = 0; v < 2; ++v) buf[v] = (float *)take(vol);
+	for (float *&im : pl.img) im = (float *)take(img);
+	pl.gk = (float *)take(align_up((size_t)ks * ks * sizeof(float), 256));
+	for (int v = 0; v < 2; ++v) pl.cplan[v] = (pl.cplan_bytes && v < nplan) ? take(pl.cplan_bytes) : nullptr;
+	pl.total = off;
+	return pl;
+}
+
+void StageTimer::mark(int stage)
+{
+	if (!on) return;
+	hipEvent_t e;
+	(void)hipEventCreate(&e);
+	(void)hipEventRecord(e, st);
+	ev.push_back(e);
+	tag.push_back(stage);
+}
+void StageTimer::collect(float out[MC_N_STAGES])
+{
+	for (int i = 0; i < MC_N_STAGES; ++i) out[i] = 0;
+	if (!on || ev.empty()) return;
+	(void)hipEventSynchronize(ev.back());
+	for (size_t i = 1; i < ev.size(); ++i) {
+		float ms = 0;
+		(void)hipEventElapsedTime(&ms, ev[i - 1], ev[i]);
+		if (tag[i] >= 0 && tag[i] < MC_N_STAGES) out[tag[i]] += ms;
+	}
+	for (auto e : ev) (void)hipEventDestroy(e);
+	ev.clear();
+}
+
+int predict_impl(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,
+                 const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
+                 float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out, float *disp_out, hipStream_t st,
+                 StageTimer &tm)
+{
+	MC_REQUIRE(p && x0 && x1 && disp_out && workspace, "mc_predict: null argument");
+	MC_REQUIRE(dims_ok(D, H, W), "mc_predict: bad dims D=%d H=%d W=%d", D, H, W);
+	MC_REQUIRE(D <= MC_SGM_MAX_D, "mc_predict: D=%d exceeds %d", D, MC_SGM_MAX_D);
+	MC_REQUIRE((featL && featR && C >= 1) || (rawL && rawR), "mc_predict: need features or raw volumes");
+	MC_REQUIRE(p->cbca_i1 >= 0 && p->cbca_i2 >= 0 && p->sgm_i >= 0, "mc_predict: negative iteration count");
+	MC_REQUIRE(p->median_k % 2 == 1 && p->median_k <= 11, "mc_predict: median_k must be odd and <= 11");
+	MC_REQUIRE(p->blur_sigma > 0, "mc_predict: blur_sigma must be > 0");
+	MC_REQUIRE(p->sm_terminate >= 0 && p->sm_terminate <= MC_SM_BILATERAL && p->sm_skip >= 0 && p->sm_skip <= MC_SKIP_BILATERAL,
+	           "mc_predict: bad sm_terminate / sm_skip");
+	const bool from_feat = featL != nullptr;
+	if (from_feat) MC_REQUIRE(p->border_n >= 0 && p->border_n < W, "mc_predict: border_n=%d out of range", p->border_n);
+	if (from_feat) MC_REQUIRE(C <= MC_JOIN_MAX_C, "mc_predict: C=%d exceeds %d (adcensus.cu:1460)", C, MC_JOIN_MAX_C);
+	const Plan pl = make_plan(p, D, H, W, workspace);   // (addresses only: nothing is touched before the two checks)
+	MC_REQUIRE(workspace_bytes >= pl.total, "mc_predict: workspace %zu < %zu bytes", workspace_bytes, pl.total);
+	MC_REQUIRE((uintptr_t)workspace % 256 == 0, "mc_predict: workspace must be 256-byte aligned");
+
+	const int64_t HW = (int64_t)H * W;
+	const int64_t V = (int64_t)D * HW;
+	int cplan_passes[2] = {0, 0};   // aggregation passes so far: the first one writes the plan, the others read it
+	bool cplan_listed[2] = {false, false};   // ... the texture route's list has been written
+	int rc;
+#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
+
+	// index 0 = left volume (direction -1), 1 = right volume (direction +1)  (main.lua:986)
+	const int direction[2] = {-1, 1};
+	const StageCounts sc = stage_counts(p);   // -sm_terminate / -sm_skip as effective iteration counts
+	const int n_cbca1 = sc.cbca1, n_sgm = sc.sgm, n_cbca2 = sc.cbca2;
+	bool sm_active = sc.active_after;
+	const bool use_cbca = (n_cbca1 + n_cbca2) > 0;
+	tm.mark(-1);
+
+	if (n_sgm > 0) RUN(sgm_prep(x0, x1, pl.maps, H, W, p->tau_so, st));
+	if (use_cbca) {  // main.lua:993-996: x0c from the LEFT image, x1c from the RIGHT, for both directions
+		RUN(cross(x0, pl.x0c, H, W, p->L1, p->tau1, st));
+		RUN(cross(x1, pl.x1c, H, W, p->L1, p->tau1, st));
+		RUN(cbca_pack(pl.x0c, pl.x1c, pl.packed, H, W, st));
+	}
+	const int cbca_cap = p->L1 - 1;  // cross(): an arm never exceeds L1-1 pixels (adcensus.cu:314)
+	tm.mark(MC_STAGE_PREP);
+
+	// ---- (A) cost volumes + CBCA-1; ends with cur[v] and its layout ----
+	// Internal (H,W,ds) volumes use the padded pixel stride ds = Dp (multiple of 4) so that
+	// every lane's run of 4 disparities is one aligned 16-byte access.
+	const int ds = pl.Dp;
+	const float *cur[2];
+	auto other = [&](int v) -> float * { return cur[v] == pl.bufA[v] ? pl.bufB[v] : pl.bufA[v]; };
+	bool hwd;  // layout of cur[]
+	// direction +1 (the right volume) is skipped where the reference skips it: dataset mb outside `-a predict`
+	// (mb_directions, main.lua:953-955) -- only when nothing of it is asked for
+	const int nvol = (p->left_only && !p->lr_check && !volR_out && !dispR0_out) ? 1 : 2;
+	// n CBCA iterations on the (D,H,W) volumes, ping-pong between the two buffers of each side (instead of vol:copy(tmp)).
+	// Where the pair's route may be the texture one (cfg.lean), the iterations go in PAIRS: cbca_lean2x runs two passes in one launch
+	// (cur -> dst) out of a list written once per pair and direction; the kernels of the other routes -- which one runs is decided on
+	// the device by the route word, the others stand down at their first instruction -- take the same two passes through the SGM's
+	// scratch volume (cur -> bufC -> dst), so that every route ends in the same buffer.  An odd last iteration is a single pass.
+	auto cbca_iterations = [&](int n) -> int {
+		const bool packed_ok = cbca_cap <= 254 && packed_dims_ok(H, W);  // packed lengths saturate at 255
+		for (int v = 0; v < nvol; ++v) {
+			// the plan area serves whichever kernel the pair's route word picks: the tile kernel's plan (written by its first pass) or, on
+			// textures, the records of the outputs whose support is not the minimal 3 x 3 -- written HERE, before the direction's first pass
+			// (route-gated, on the device), so that every later launch finds the list's state final: usable -> cbca_lean2x per pair of passes
+			// and the strip kernel for a single one; unusable (flat regions next to the texture) -> the tile kernel
+			const bool planned = packed_ok && pl.cplan[v] && cbca_cap > 4 && cbca_cap <= 13 && cbca_lean_fits(D, H, W, pl.cplan_bytes, true);
+			if (planned && n > 0 && !cplan_listed[v]) {
+				const int rc1 = cbca_classify(pl.packed, pl.cplan[v], pl.cplan_bytes, D, H, W, direction[v], CR_STRIP, 0, 0, st, true);
+				if (rc1) return rc1;
+				cplan_listed[v] = true;
+			}
+			for (int i = 0; i < n;) {
+				float *dst = other(v);
+				CbcaCfg cfg;
+				cfg.plan = pl.cplan[v];
+				cfg.plan_bytes = pl.cplan_bytes;
+				cfg.planned = planned;
+				const bool two = planned && i + 1 < n;
+				cfg.lean = cfg.lean_two_pass = two;   // (a single pass: the strip kernel serves the texture route itself)
+				float *mid = two ? pl.bufC[v] : dst;
+				for (int half = 0; half < (two ? 2 : 1); ++half) {   // the routes that take one pass per launch
+					cfg.plan_mode = pl.cplan[v] ? (cplan_passes[v]++ == 0 ? 1 : 2) : 0;
+					const float *src = half == 0 ? cur[v] : mid;
+					float *to = (two && half == 0) ? mid : dst;
+					const int rc2 = packed_ok ? cbca_by_arms(pl.packed, src, to, D, H, W, direction[v], cbca_cap, st, cfg)
+					                          : cbca(pl.x0c, pl.x1c, src, to, D, H, W, direction[v], st);
+					if (rc2) return rc2;
+				}
+				if (two) {
+					const int rc3 = cbca_lean2x(pl.packed, pl.cplan[v], pl.cplan_bytes, cur[v], dst, D, H, W, direction[v], CR_STRIP, st, cfg);
+					if (rc3) return rc3;
+				}
+				cur[v] = dst;
+				i += two ? 2 : 1;
+			}
+		}
+		return 0;
+	};
+	// (C + 64: the kernels pad the channel count to their k-step sizes and add channel offsets to range-checked 32-bit byte
+	// offsets -- no padded channel's offset may wrap)
+	const bool join_fits = (int64_t)W * ((D + 3) / 4 * 4) * 4 < ((int64_t)1 << 31) && ((int64_t)(C + 64) * HW + W) * 4 < ((int64_t)1 << 31);
+	if (from_feat && n_cbca1 == 0 && n_sgm > 0 && join_fits) {
+		// fast path: StereoJoin straight into (H,W,ds) with NaN fill and fix_border folded in
+		RUN(stereo_join_hwd(featL, featR, pl.bufA[0], pl.bufA[1], C, D, ds, H, W, p->border_n, st));
+		cur[0] = pl.bufA[0]; cur[1] = pl.bufA[1];
+		hwd = true;
+		tm.mark(MC_STAGE_JOIN);
+	} else {
+		if (from_feat) {  // main.lua:946-949
+			RUN(fill_nan(pl.bufA[0], V, st));
+			RUN(fill_nan(pl.bufA[1], V, st));
+			RUN(stereo_join_dhw(featL, featR, pl.bufA[0], pl.bufA[1], C, D, H, W, st));
+			RUN(fix_border(pl.bufA[0], D, H, W, p->border_n, -1, st));
+			RUN(fix_border(pl.bufA[1], D, H, W, p->border_n, 1, st));
+			cur[0] = pl.bufA[0]; cur[1] = pl.bufA[1];
+		} else {
+			cur[0] = rawL; cur[1] = rawR;
+		}
+		hwd = false;
+		tm.mark(MC_STAGE_JOIN);
+		RUN(cbca_iterations(n_cbca1));  // main.lua:998-1001 (ping-pong instead of vol:copy(tmp))
+		tm.mark(MC_STAGE_CBCA);
+	}
+
+	// ---- (B) SGM, main.lua:1007-1030 ----
+	float *dispv[2] = {pl.img[0], pl.img[1]};  // [0] = left disparity (disp[2] in Lua), [1] = right
+	bool have_disp = false;
+	if (n_sgm > 0) {
+		if (!hwd) {  // vol:transpose(2,3):transpose(3,4):clone(), main.lua:1008
+			for (int v = 0; v < nvol; ++v) {
+				float *dst = other(v);
+				RUN(transpose(cur[v], dst, D, HW, HW, ds, 1.0f, st));
+				cur[v] = dst;
+			}
+			hwd = true;
+			tm.mark(MC_STAGE_LAYOUT);
+		}
+		for (int it = 0; it < n_sgm; ++it) {
+			// out:zero(); sgm2(...); vol:copy(out):div(4)  (main.lua:1013-1018): the zero is folded
+			// into the first sweep (0 + L_0) and the /4 into the last
+			const float *Cv[2] = {cur[0], cur[1]};
+			float *outv[2] = {other(0), other(1)};
+			const bool am = (it == n_sgm - 1) && n_cbca2 == 0;
+			// the right volume's final costs: where no CBCA-2 follows, only right.bin reads them (sub-pixel refinement reads the
+			// left volume, the LR check the arg-min maps that the up sweep writes regardless) -- not stored unless asked for
+			const unsigned drop_final = (am && nvol == 2 && !volR_out) ? 2u : 0u;
+			RUN(sgm_sweeps(Cv, outv, pl.bufC, am ? dispv : nullptr, direction, nvol, H, W, D, ds, pl.maps, p->pi1, p->pi2, p->alpha1,
+			               p->sgm_q1, p->sgm_q2, true, drop_final, st));
+			have_disp = am;
+			cur[0] = outv[0]; cur[1] = outv[1];
+		}
+		tm.mark(MC_STAGE_SGM);
+		if (n_cbca2 > 0) {  // back to (D,H,W): vol:copy(out:transpose(3,4):transpose(2,3)), main.lua:1019-1020
+			for (int v = 0; v < nvol; ++v) {
+				float *dst = other(v);
+				RUN(transpose(cur[v], dst, HW, D, ds, HW, 1.0f, st));
+				cur[v] = dst;
+			}
+			hwd = false;
+			tm.mark(MC_STAGE_LAYOUT);
+		}
+	}
+	if (!hwd) {  // CBCA-2, main.lua:1033-1039
+		RUN(cbca_iterations(n_cbca2));
+		tm.mark(MC_STAGE_CBCA);
+	}
+
+	// ---- argmin, main.lua:1049-1050 ----
+	// an (H,W,ds) volume exists only around the SGM, whose last up sweep folds the arg-min in where no CBCA-2 follows (have_disp)
+	MC_REQUIRE(have_disp || !hwd, "mc_predict: an (H,W,D) volume without its arg-min");
+	if (!have_disp) {
+		for (int v = 0; v < nvol; ++v) RUN(argmin_dhw(cur[v], dispv[v], D, H, W, 0, st));
+	}
+	// ---- left.bin / right.bin contents, main.lua:1042-1047 ----
+	float *vout[2] = {volL_out, volR_out};
+	for (int v = 0; v < nvol; ++v) {
+		if (!vout[v]) continue;
+		if (hwd) RUN(transpose(cur[v], vout[v], HW, D, ds, HW, 1.0f, st));
+		else RUN(scale(cur[v], vout[v], V, 1.0f, st));
+	}
+	if (dispL0_out) RUN(scale(dispv[0], dispL0_out, HW, 1.0f, st));
+	if (dispR0_out) RUN(scale(dispv[1], dispR0_out, HW, 1.0f, st));
+	tm.mark(MC_STAGE_ARGMIN);
+
+	// ---- (C) post-processing on the LEFT disparity, main.lua:1054-1081 ----
+	// every stage reads `d` and writes the next free image; -sm_skip / -sm_terminate drop stages (main.lua:1057-1079)
+	float *d = dispv[0];
+	float *outl = pl.img[4];
+	int nfree = 0;
+	float *freeimg[3] = {pl.img[2], pl.img[3], pl.img[5]};
+	auto next = [&]() -> float * {
+		float *r = freeimg[nfree % 3];
+		if (r == d) r = freeimg[++nfree % 3];
+		++nfree;
+		return r;
+	};
+	// one stage: if it is active and not skipped it runs into the next free image, which becomes `d`; then -sm_terminate applies
+	auto stage = [&](int skip, int terminate, auto &&run) -> int {
+		if (sm_active && p->sm_skip != skip) {
+			float *o = next();
+			if (const int rc1 = run(o)) return rc1;
+			d = o;
+		}
+		sm_active = sm_active && p->sm_terminate != terminate;
+		return 0;
+	};
+	if (p->lr_check) {
+		RUN(outlier_detection(d, dispv[1], outl, H, W, D, st));
+		RUN(stage(MC_SKIP_OCCLUSION, MC_SM_OCCLUSION, [&](float *o) { return interpolate_occlusion(d, outl, o, H, W, st); }));
+		RUN(stage(MC_SKIP_OCCLUSION, MC_SM_MISMATCH, [&](float *o) { return interpolate_mismatch(d, outl, o, H, W, st); }));
+	}
+	// subpixel on the LEFT volume (vol of the last loop iteration, main.lua:1068)
+	RUN(stage(MC_SKIP_SUBPIXEL, MC_SM_SUBPIXEL, [&](float *o) {
+		return hwd ? subpixel(d, cur[0], o, D, H, W, 1, ds, st) : subpixel(d, cur[0], o, D, H, W, HW, 1, st);
+	}));
+	RUN(stage(MC_SKIP_MEDIAN, MC_SM_MEDIAN, [&](float *o) { return median2d(d, o, H, W, p->median_k, st); }));
+	if (sm_active && p->sm_skip != MC_SKIP_BILATERAL) {
+		GaussianK k;
+		RUN(gaussian_cached(p->blur_sigma, k));
+		const hipError_t e = hipMemcpyAsync(pl.gk, k.data, k.n * sizeof(float), hipMemcpyHostToDevice, st);  // pinned source
+		if (e != hipSuccess) {
+			set_error("mc_predict: kernel upload: %s", hipGetErrorString(e));
+			return (int)e;
+		}
+		RUN(mean2d(d, pl.gk, disp_out, H, W, gaussian_ks(p->blur_sigma), p->blur_t, st));
+	} else {
+		RUN(scale(d, disp_out, HW, 1.0f, st));  // the last stage that ran is the result
+	}
+	tm.mark(MC_STAGE_POST);
+#undef RUN
+	return 0;
+}
+
+}  // namespace mc

@@ -19,7 +19,7 @@
 // classes of 4 consecutive pixels s..s+3 (ascending for direction +1,
 // descending for -1) so that a lane fetches the classes of its VPL
 // disparities with VPL/4 byte loads.
-#include "mc_common.h"
+#include "launchers.h"
 
 // cache policy of the volume accesses: nt (bit 1) -- every cost run is read or written once per sweep; streaming them keeps
 // the edge-class maps (re-read by every line) in L2
@@ -460,23 +460,23 @@ int sgm_contract_violations(const float *vol, int H, int W, int D, unsigned *cou
 	return check_launch("sgm_contract");
 }
 
-size_t sgm_maps_bytes(int H, int W)
+// the maps sgm_prep writes and the sweeps read: cls0[4][plane] then win[2][4][H][Wm] (see SgmPassArgs); cls0 / win = byte offsets
+struct SgmMaps { int Wm; size_t plane, cls0, win, bytes; };
+static SgmMaps sgm_maps(int H, int W)
 {
-	const size_t Wm = (size_t)W + 2 * SGM_PADW;
+	const int Wm = W + 2 * SGM_PADW;
 	const size_t plane = ((size_t)H * W + 3 + 4) / 4 * 4;  // dword-aligned class planes (+4: the dword read may straddle)
-	size_t b = 4 * plane + (size_t)8 * H * Wm;
-	return (b + 255) & ~(size_t)255;
+	return {Wm, plane, 0, 4 * plane, (4 * plane + (size_t)8 * H * Wm + 255) & ~(size_t)255};
 }
+
+size_t sgm_maps_bytes(int H, int W) { return sgm_maps(H, W).bytes; }
 
 int sgm_prep(const float *x0, const float *x1, void *maps, int H, int W, float tau_so, hipStream_t st)
 {
-	const int Wm = W + 2 * SGM_PADW;
-	const size_t plane = ((size_t)H * W + 3 + 4) / 4 * 4;
-	uint8_t *cls0 = (uint8_t *)maps;
-	uint8_t *win = cls0 + 4 * plane;
-	const int64_t total = (int64_t)4 * H * Wm;
-	hipLaunchKernelGGL(sgm_prep_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, x0, x1, cls0, win, H, W, Wm, (int64_t)plane,
-	                   tau_so);
+	const SgmMaps m = sgm_maps(H, W);
+	const int64_t total = (int64_t)4 * H * m.Wm;
+	hipLaunchKernelGGL(sgm_prep_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, x0, x1, (uint8_t *)maps + m.cls0, (uint8_t *)maps + m.win, H, W,
+	                   m.Wm, (int64_t)m.plane, tau_so);
 	return check_launch("sgm_prep");
 }
 
@@ -550,10 +550,11 @@ int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2
 	}
 	A.nvol = nvol;
 	A.H = H; A.W = W; A.D = D; A.ds = ds;
-	A.Wm = W + 2 * SGM_PADW;
-	A.cls0 = (const uint8_t *)maps;
-	A.cls_plane = (int64_t)(((size_t)H * W + 3 + 4) / 4 * 4);
-	A.win = A.cls0 + 4 * A.cls_plane;
+	const SgmMaps m = sgm_maps(H, W);
+	A.Wm = m.Wm;
+	A.cls0 = (const uint8_t *)maps + m.cls0;
+	A.cls_plane = (int64_t)m.plane;
+	A.win = (const uint8_t *)maps + m.win;
 	// adcensus.cu:595-605 -- float divisions exactly as written there
 	A.P1[0] = pi1; A.P2[0] = pi2;
 	A.P1[1] = pi1 / q1; A.P2[1] = pi2 / q1;

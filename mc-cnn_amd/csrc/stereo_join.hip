@@ -3,7 +3,7 @@
 // StereoJoin_ (adcensus.cu:1455-1477): s(x,d) = -sum_c L[c,y,x] * R[c,y,x-d], accumulated
 // with c ascending as sum = fma(-L, R, sum) (nvcc contracts `sum -= a*b`); the value goes to
 // volL[d,y,x] and volR[d,y,x-d].  The fma chain order is kept, so results are bit-identical.
-#include "mc_common.h"
+#include "launchers.h"
 #include <type_traits>
 
 namespace mc {
@@ -413,30 +413,22 @@ int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, 
 	// mc_predict's (H,W,Dp) workspace volumes only: the owner kernel's 16-byte runs need them
 	MC_REQUIRE(ds % 4 == 0 && (uintptr_t)volL % 16 == 0 && (uintptr_t)volR % 16 == 0,
 	           "stereo_join_hwd: the volumes must be 16-byte aligned with a pixel stride ds %% 4 == 0 (ds = %d)", ds);
+	const char *what = "stereo_join_hwd";
 	if (ks <= 32) {
 		const int tiles_own = ((W + 31) / 32 + MC_JOIN_NT - 1) / MC_JOIN_NT;   // groups of MC_JOIN_NT 32-pixel tiles per image row and volume
 		const dim3 grid_o((unsigned)(rows8 * ((2 * tiles_own + MC_JOIN_WPB - 1) / MC_JOIN_WPB) * 8)), block_o(64 * MC_JOIN_WPB);
 		if (ks <= 8) hipLaunchKernelGGL((join_owner_kernel<8>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own);
 		else if (ks <= 16) hipLaunchKernelGGL((join_owner_kernel<16>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own);
 		else hipLaunchKernelGGL((join_owner_kernel<32>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own);
-		int rc = check_launch("stereo_join_hwd (owner tiles)");
-		if (rc || n <= 0) return rc;
-		hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)H * n * 64, 256)), block, 0, st, volL, D, ds, H, W, n, -1);
-		hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)H * n * 64, 256)), block, 0, st, volR, D, ds, H, W, n, 1);
-		return check_launch("fix_border_hwd");
+		what = "stereo_join_hwd (owner tiles)";
+	} else {   // C > 64 (ks > 32, MC_JOIN_MAX_C = 128: ks <= 64)
+		const int tiles = (W + D - 1 + 31) / 32;  // incl. the virtual tiles right of the image (right volume's NaN triangle)
+		const int blocks_per_row = (tiles + 3) / 4;
+		const dim3 grid((unsigned)(rows8 * blocks_per_row * 8));
+		if (ks <= 56) hipLaunchKernelGGL((join_mfma_kernel<56>), grid, block, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles);
+		else hipLaunchKernelGGL((join_mfma_kernel<64>), grid, block, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles);
 	}
-	// C > 64 (ks > 32, MC_JOIN_MAX_C = 128: ks <= 64)
-	const int tiles = (W + D - 1 + 31) / 32;  // incl. the virtual tiles right of the image (right volume's NaN triangle)
-	const int blocks_per_row = (tiles + 3) / 4;
-	const dim3 grid((unsigned)(rows8 * blocks_per_row * 8));
-#define MC_JOIN_LAUNCH(KS)                                                                                                  \
-	do {                                                                                                                    \
-		hipLaunchKernelGGL((join_mfma_kernel<KS>), grid, block, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles);             \
-	} while (0)
-	if (ks <= 56) MC_JOIN_LAUNCH(56);
-	else MC_JOIN_LAUNCH(64);
-#undef MC_JOIN_LAUNCH
-	int rc = check_launch("stereo_join_hwd");
+	const int rc = check_launch(what);
 	if (rc || n <= 0) return rc;
 	hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)H * n * 64, 256)), block, 0, st, volL, D, ds, H, W, n, -1);
 	hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)H * n * 64, 256)), block, 0, st, volR, D, ds, H, W, n, 1);

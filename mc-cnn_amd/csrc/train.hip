@@ -21,29 +21,7 @@
 #include "mc_common.h"
 #include "../../include/mc_train.h"
 
-#include <stdarg.h>
-
 namespace mc {
-
-static thread_local char g_train_err[512] = "";
-
-void set_error(const char *fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(g_train_err, sizeof(g_train_err), fmt, ap);
-	va_end(ap);
-}
-
-int check_launch(const char *what)
-{
-	const hipError_t e = hipPeekAtLastError();
-	if (e != hipSuccess) {
-		set_error("%s: %s", what, hipGetErrorString(e));
-		return (int)e;
-	}
-	return 0;
-}
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -470,7 +448,7 @@ extern "C" {
 
 int mc_train_version(void) { return MC_TRAIN_ABI_VERSION; }
 
-const char *mc_train_last_error(void) { return g_train_err; }
+const char *mc_train_last_error(void) { return last_error(); }
 
 size_t mc_train_workspace_bytes(int n_pairs)
 {

@@ -81,6 +81,46 @@ def test_plan_and_workspace_sizes(mc):
         2 * lib.mc_cbca_plan_bytes(256, 1000, 1500)
 
 
+# mc_predict_workspace_bytes as the build of the commit before the workspace got its single walk returned it
+WS_SHAPES = ((228, 370, 1226), (256, 1000, 1500), (7, 33, 130), (1, 1, 1))   # (D, H, W)
+WS_BYTES = {
+    # preset, overrides
+    ("kitti_fast", ()): (2519785984, 9338343168, 1449472, 34048),
+    ("kitti_slow", ()): (3281484800, 12106580224, 1904640, 63232),
+    ("mb_slow", ()): (3281479936, 12106575360, 1899776, 58368),
+    ("kitti_slow", (("left_only", 1), ("lr_check", 0))): (2900633344, 10722459648, 1675008, 46592),
+    ("kitti_slow", (("cbca_i1", 1), ("cbca_i2", 0))): (2519781888, 9338339072, 1445376, 29952),
+    ("mb_slow", (("L1", 20),)): (2519777024, 9338334208, 1440512, 25088),
+}
+
+
+def test_predict_workspace_bytes_are_pinned(mc):
+    for (name, over), want in WS_BYTES.items():
+        p = mc.make_params(name)
+        for k, v in over:
+            setattr(p, k, v)
+        got = tuple(mc._lib.lib.mc_predict_workspace_bytes(C.byref(p), 0, D, H, W) for D, H, W in WS_SHAPES)
+        assert got == want, (name, over)
+
+
+def test_each_library_keeps_its_own_error_message(mc, tmp_path):
+    from mc_cnn_amd import _train_lib
+    lib, tl = mc._lib.lib, _train_lib.load()
+    EINVAL = -22
+    assert lib.mc_ad(1, 1, 1, 4, 8, 8, 0, None) == EINVAL
+    assert lib.mc_last_error() == b"mc_ad: direction must be -1 or 1"
+    before = tl.mc_train_last_error()
+    assert b"mc_ad" not in before
+    assert tl.mc_train_sample(None, None, 1, 8, 8, None, 1, None, None, 1, None, None) == EINVAL
+    assert tl.mc_train_last_error() == b"train: null image / nnz pointer"
+    assert lib.mc_last_error() == b"mc_ad: direction must be -1 or 1"          # untouched by the other library
+    h, w = C.c_int(), C.c_int()
+    missing = str(tmp_path / "missing.png").encode()
+    assert lib.mc_read_png16(missing, None, 0, C.byref(h), C.byref(w)) == EINVAL   # set by hostio.cpp
+    assert lib.mc_last_error() == b"mc_read_png16: cannot open " + missing
+    assert tl.mc_train_last_error() == b"train: null image / nnz pointer"     # and the other direction
+
+
 def test_gaussian_host_matches_main_lua(mc):
     """gaussian(sigma), main.lua:528-540, runs on the host in doubles: checked here without a GPU."""
     import math

@@ -1,4 +1,4 @@
-// Error reporting of libmcadcensus.so and libmctrain.so (error.hip, linked into each: every library has its own
+// Error reporting of libmcadcensus.so, libmctrain.so and libmctrainslow.so (error.hip, linked into each: every library has its own
 // thread-local message).  No HIP header: plain C++ units (hostio.cpp) include this too.
 #pragma once
 #include "../../include/mc_adcensus.h"

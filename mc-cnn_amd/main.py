@@ -17,8 +17,9 @@ w1,b1,...,w<l1>,b<l1> (w_i: (fm, in, 3, 3); arch slow also fw1,fb1,...), or `ran
 (`-a train_tr` trains one: see below).  Hyper-parameter flags (-L1 -tau1 -cbca_i1 -cbca_i2 -pi1 -pi2 -sgm_i
 -sgm_q1 -sgm_q2 -alpha1 -tau_so -blur_sigma -blur_t) default to main.lua's per-(dataset, arch) tables.
 
-`-a train_tr | train_all` (kitti | kitti2015, arch fast; main.lua:602-890) train the net on the GPU from `-data_dir`
-(train.py, libmctrain.so) and save net/net_<args>.t7; train_tr then runs test_te.  `-a test_te | test_all`
+`-a train_tr | train_all` (kitti | kitti2015; main.lua:602-890) train the net on the GPU from `-data_dir` (arch fast:
+train.py, libmctrain.so; arch slow: train_slow.py, libmctrainslow.so, with train_slow.parse's flags) and save
+net/net_<args>.t7; train_tr then runs test_te.  `-a test_te | test_all`
 (main.lua:1121-1138, 1172-1293) predict the dataset's test (all) pairs with -net_fname and print `runtime err` per pair and
 the mean error.  Training flags keep main.lua's names and defaults; -epochs and -max_steps shorten a run.  `-at 1` trains
 and tests on data.kitti and data.kitti2015 together (main.lua:403-426).  `python -m mc_cnn_amd.preprocess_kitti` writes
@@ -81,7 +82,8 @@ def parse(argv):
     opt = ap.parse_args(argv[2:])
     if opt.a not in ("predict", "time") and (opt.a not in TRAIN_ACTIONS or dataset not in ("kitti", "kitti2015") or arch != "fast"):
         raise SystemExit("main.py: -a %s is not supported for %s %s; training and testing cover -a %s for "
-                         "{kitti|kitti2015} fast only (arch slow, Middlebury and -a submit are out of scope)"
+                         "{kitti|kitti2015} fast only (arch slow trains through train_slow.parse, which main() routes "
+                         "{kitti|kitti2015} slow to; Middlebury and -a submit are out of scope)"
                          % (opt.a, dataset, arch, " | ".join(TRAIN_ACTIONS)))
     if getattr(opt, "at", 0) == 1 and opt.data_dir:
         raise SystemExit("main.py: -at 1 reads data.kitti and data.kitti2015 together (main.lua:403-426) and takes no -data_dir")
@@ -124,13 +126,27 @@ def add_train_flags(ap, dataset):
 FC_SHAPES = {"kitti": (4, 384), "kitti2015": (4, 384), "mb": (3, 384)}  # (l2, nh2), main.lua:76-77, 123-124
 
 
+_t7_cache = {}   # the latest parsed .t7: arch slow reads its two nets from one file, and an ASCII net of 870 449 floats parses in seconds
+
+
+def reference_nets(net_fname, arch):
+    """t7.load_reference_net, parsed once per (file, size, mtime)."""
+    import os
+    from . import t7
+    st = os.stat(net_fname)
+    key = (os.path.abspath(net_fname), arch, st.st_size, st.st_mtime_ns)
+    if key not in _t7_cache:
+        _t7_cache.clear()
+        _t7_cache[key] = t7.load_reference_net(net_fname, arch)
+    return _t7_cache[key]
+
+
 def load_net(net_fname, dataset, arch, n_input_plane=1):
     """[(w, b)] of the feature net: from the reference's `.t7` (torch.save(..., 'ascii'), main.lua:587-600), an .npz, or
     seeded random (`random:<seed>`)."""
     l1, fm = NET_SHAPES[(dataset, arch)]
     if net_fname.endswith(".t7"):
-        from . import t7
-        layers = t7.load_reference_net(net_fname, arch)[0]
+        layers = reference_nets(net_fname, arch)[0]
         if not layers:
             raise ValueError("%s: no SpatialConvolution modules found" % net_fname)
         return layers
@@ -152,8 +168,7 @@ def load_fc(net_fname, dataset):
     or seeded random."""
     l1, fm = NET_SHAPES[(dataset, "slow")]
     if net_fname.endswith(".t7"):
-        from . import t7
-        fc = t7.load_reference_net(net_fname, "slow")[1]
+        fc = reference_nets(net_fname, "slow")[1]
         if not fc:
             raise ValueError("%s: no SpatialConvolution1_fw modules found" % net_fname)
         return fc
@@ -213,8 +228,19 @@ def features_fast(x_batch, layers):
     return out
 
 
+def trains_slow(argv):
+    """{kitti|kitti2015} slow -a train_tr|train_all|test_te|test_all: train_slow.parse's command lines (parse refuses them)."""
+    return (len(argv) >= 2 and argv[0] in ("kitti", "kitti2015") and argv[1] == "slow" and "-a" in argv[2:-1]
+            and argv[argv.index("-a", 2) + 1] in TRAIN_ACTIONS)
+
+
 def main(argv=None):
-    dataset, arch, opt, prm = parse(list(sys.argv[1:] if argv is None else argv))
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if trains_slow(argv):
+        from . import train_slow
+        dataset, arch, opt, prm = train_slow.parse(argv)
+    else:
+        dataset, arch, opt, prm = parse(argv)
     import torch
     from .predict import Workspace, stereo_predict_fused
     if arch not in ("fast", "slow", "ad", "census"):
@@ -246,11 +272,16 @@ def main(argv=None):
     if opt.a in TRAIN_ACTIONS:
         from . import train
         if opt.a in ("train_tr", "train_all"):   # main.lua:602-890
-            opt.net_fname = train.train(dataset, arch, opt, list(sys.argv[1:] if argv is None else argv)[2:], dev)
+            if arch == "slow":
+                opt.net_fname = train_slow.train(dataset, opt, argv[2:], dev)
+            else:
+                opt.net_fname = train.train(dataset, arch, opt, argv[2:], dev)
             if opt.a == "train_all":            # main.lua:884-887 goes on to submit, which is out of scope
                 return 0
             opt.a = "test_te"
             layers[:] = device_layers(load_net(opt.net_fname, dataset, arch), dev)
+            if arch == "slow":
+                fc_layers[:] = load_fc(opt.net_fname, dataset)
         train.evaluate(dataset, opt, run, dev)   # main.lua:1121-1138, 1172-1293
         return 0
     if opt.a == "time":  # main.lua:1140-1167

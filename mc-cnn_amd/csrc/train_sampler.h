@@ -1,5 +1,6 @@
-// The patch sampler of the training libraries (libmctrain.so, libmctrainslow.so): one device function, so that both draw
-// the same patches bit for bit.
+// The patch sampler of the training libraries (libmctrain.so, libmctrainslow.so, libmctrainmb.so): one device function,
+// so that all draw the same patches bit for bit.  The patch size PS is a template parameter: 9 for the KITTI nets (WS), 11 for
+// Middlebury's five-layer net.
 #pragma once
 #include "mc_common.h"
 #include "../../include/mc_train.h"
@@ -34,8 +35,9 @@ __device__ inline void cubic_coeffs(float x, float c[4])
 	c[3] = 1.f - c[0] - c[1] - c[2];
 }
 
-// One output pixel (dx, dy) of a 9 x 9 patch of image `src` (H x W) warped by make_patch's matrix for
+// One output pixel (dx, dy) of a PS x PS patch of image `src` (H x W) warped by make_patch's matrix for
 // (row, col, scale, phi, trans, hshear), then * contrast + brightness.
+template <int PS>
 __device__ float sample_pixel(const float *__restrict__ src, int H, int W, double row, double col, const float *p, int dx, int dy)
 {
 	// p: scale_x scale_y phi trans_x trans_y hshear brightness contrast
@@ -48,7 +50,7 @@ __device__ float sample_pixel(const float *__restrict__ src, int H, int W, doubl
 		m = mul32(t, m);
 	}
 	{ const double t[6] = {1, (double)p[5], 0, 0, 1, 0}; m = mul32(t, m); }
-	{ const double t[6] = {1, 0, (WS - 1) / 2.0, 0, 1, (WS - 1) / 2.0}; m = mul32(t, m); }
+	{ const double t[6] = {1, 0, (PS - 1) / 2.0, 0, 1, (PS - 1) / 2.0}; m = mul32(t, m); }
 	double M[6];
 	for (int i = 0; i < 6; ++i) M[i] = (double)(float)m.m[i];   // torch.FloatTensor(m), then OpenCV's convertTo(CV_64F)
 	// warpAffine without WARP_INVERSE_MAP inverts the matrix
@@ -90,12 +92,13 @@ __device__ float sample_pixel(const float *__restrict__ src, int H, int W, doubl
 	return sum * p[7] + p[6];   // dst:mul(contrast):add(brightness)
 }
 
-// Pixel t (0 .. 3*81-1) of pair `pair`'s three patches.  Rows outside nnz or images outside x0 read 0: the warp's result is
+// Pixel t (0 .. 3*PS*PS-1) of pair `pair`'s three patches.  Rows outside nnz or images outside x0 read 0: the warp's result is
 // 0, then * contrast + brightness like any patch that lies outside its image.
+template <int PS>
 __device__ float sample_pair_pixel(const float *__restrict__ x0, const float *__restrict__ x1, int n_img, int H, int W,
                                    const float *__restrict__ nnz, int64_t n_nnz, int row, const float *__restrict__ prm, int t)
 {
-	const int patch = t / (WS * WS), pix = t - patch * WS * WS;
+	const int patch = t / (PS * PS), pix = t - patch * PS * PS;
 	float p[8];
 	for (int k = 0; k < 8; ++k) p[k] = prm[(patch == 0 ? 2 : 10) + k];
 	if (row < 0 || row >= n_nnz) return 0.f * p[7] + p[6];
@@ -105,7 +108,7 @@ __device__ float sample_pair_pixel(const float *__restrict__ x0, const float *__
 	const double dim3 = z[1], dim4 = z[2], d = z[3];
 	const double col = patch == 0 ? dim4 : dim4 - d + (double)prm[patch == 1 ? 0 : 1];
 	const float *src = (patch == 0 ? x0 : x1) + (int64_t)(img - 1) * H * W;
-	return sample_pixel(src, H, W, dim3, col, p, pix % WS, pix / WS);
+	return sample_pixel<PS>(src, H, W, dim3, col, p, pix % PS, pix / PS);
 }
 
 }  // namespace mc

@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(NT) tower_forward_kernel(const float *__restri
 	const int pair = blockIdx.x, t = threadIdx.x;
 	if (t < NPIX) {
 		if (SAMPLE) {
-			const float v = sample_pair_pixel(x0, x1, n_img, H, W, nnz, n_nnz, rows[pair], prm + (int64_t)pair * NPRM, t);
+			const float v = sample_pair_pixel<WS>(x0, x1, n_img, H, W, nnz, n_nnz, rows[pair], prm + (int64_t)pair * NPRM, t);
 			lds[L_X + t] = v;
 			xs[(int64_t)pair * NPIX + t] = v;
 		} else {

@@ -23,7 +23,9 @@ net/net_<args>.t7; train_tr then runs test_te.  `-a test_te | test_all`
 (main.lua:1121-1138, 1172-1293) predict the dataset's test (all) pairs with -net_fname and print `runtime err` per pair and
 the mean error.  Training flags keep main.lua's names and defaults; -epochs and -max_steps shorten a run.  `-at 1` trains
 and tests on data.kitti and data.kitti2015 together (main.lua:403-426).  `python -m mc_cnn_amd.preprocess_kitti` writes
-both sets from the KITTI archives (preprocess_kitti.lua).
+both sets from the KITTI archives (preprocess_kitti.lua).  `mb fast -a train_tr | train_all | test_te` train and test
+Middlebury's five-layer fast net (train_mb.py, libmctrainmb.so, with train_mb.parse's flags) from preprocess_mb.py's
+`data.mb.<rect>_<color>`; mb slow training, -a test_all on mb and -a submit are out of scope.
 """
 import argparse
 import sys
@@ -83,7 +85,8 @@ def parse(argv):
     if opt.a not in ("predict", "time") and (opt.a not in TRAIN_ACTIONS or dataset not in ("kitti", "kitti2015") or arch != "fast"):
         raise SystemExit("main.py: -a %s is not supported for %s %s; training and testing cover -a %s for "
                          "{kitti|kitti2015} fast only (arch slow trains through train_slow.parse, which main() routes "
-                         "{kitti|kitti2015} slow to; Middlebury and -a submit are out of scope)"
+                         "{kitti|kitti2015} slow to, mb fast -a train_tr | train_all | test_te through train_mb.parse; mb slow "
+                         "training, -a test_all on mb and -a submit are out of scope)"
                          % (opt.a, dataset, arch, " | ".join(TRAIN_ACTIONS)))
     if getattr(opt, "at", 0) == 1 and opt.data_dir:
         raise SystemExit("main.py: -at 1 reads data.kitti and data.kitti2015 together (main.lua:403-426) and takes no -data_dir")
@@ -97,7 +100,7 @@ def parse(argv):
 
 TRAIN_ACTIONS = ("train_tr", "train_all", "test_te", "test_all")
 
-# main.lua:33-64 (augmentation, per dataset) and 207-220, 236-248 (arch fast training); the mb values are parsed only
+# main.lua:33-64 (augmentation, per dataset) and 207-220, 236-248 (arch fast training); the mb values are train_mb.parse's
 AUG_DEFAULTS = {
     "kitti": dict(hflip=0, vflip=0, rotate=7, hscale=0.9, scale=1, trans=0, hshear=0.1, brightness=0.7, contrast=1.3,
                   d_vtrans=0, d_rotate=0, d_hscale=1, d_hshear=0, d_brightness=0.3, d_contrast=1),
@@ -234,11 +237,21 @@ def trains_slow(argv):
             and argv[argv.index("-a", 2) + 1] in TRAIN_ACTIONS)
 
 
+def trains_mb(argv):
+    """mb fast -a train_tr|train_all|test_te: train_mb.parse's command lines (parse refuses them)."""
+    from .train_mb import ACTIONS
+    return (len(argv) >= 2 and argv[0] == "mb" and argv[1] == "fast" and "-a" in argv[2:-1]
+            and argv[argv.index("-a", 2) + 1] in ACTIONS)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if trains_slow(argv):
         from . import train_slow
         dataset, arch, opt, prm = train_slow.parse(argv)
+    elif trains_mb(argv):
+        from . import train_mb
+        dataset, arch, opt, prm = train_mb.parse(argv)
     else:
         dataset, arch, opt, prm = parse(argv)
     import torch
@@ -269,6 +282,15 @@ def main(argv=None):
                                         want_volumes=want_volumes)
         raw = raw_volumes_slow(features_slow(x_batch, layers), fc_layers, D, prm["border_n"])
         return stereo_predict_fused(x_batch, prm, D, raw=raw, workspace=workspace, want_volumes=want_volumes)
+    if dataset == "mb" and opt.a in TRAIN_ACTIONS:   # train_mb.parse's: train_tr | train_all | test_te
+        if opt.a != "test_te":
+            opt.net_fname = train_mb.train(opt, argv[2:], dev)
+            if opt.a == "train_all":
+                return 0
+            opt.a = "test_te"
+            layers[:] = device_layers(load_net(opt.net_fname, dataset, arch), dev)
+        train_mb.evaluate(opt, prm, run, dev)          # main.lua:1124-1130, 1183-1238
+        return 0
     if opt.a in TRAIN_ACTIONS:
         from . import train
         if opt.a in ("train_tr", "train_all"):   # main.lua:602-890

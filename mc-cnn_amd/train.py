@@ -18,8 +18,9 @@ images, then the chosen set's test images (for kitti2015 from 2015 image n_tr on
 indices and nnz image ids are shifted by 2012's n_tr.  main.lua hard-codes the two n_tr (194, 200); here each is the
 length of its set's dispnoc.bin.  The sets come from `python -m mc_cnn_amd.preprocess_kitti`.
 
-Arch slow trains through train_slow.py (libmctrainslow.so), which reuses this module's data, draws and evaluation.
-Not covered: Middlebury, -subset, -debug, -a submit, multi-GPU.
+Arch slow trains through train_slow.py (libmctrainslow.so), which reuses this module's data, draws and evaluation;
+`mb fast` through train_mb.py (libmctrainmb.so), which reuses the draws, the epoch schedule, the saved net and the error.
+Not covered: mb slow, -subset, -debug, -a submit, multi-GPU.
 """
 import math
 import os

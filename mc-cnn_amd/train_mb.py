@@ -1,0 +1,395 @@
+"""`main.lua mb fast -a train_tr | train_all | test_te` (main.lua:455-490, 602-890, 1121-1131, 1183-1238) on the MI355X.
+
+Middlebury's fast net is `-l1 5 -fm 64` (main.lua:271-272): five valid 3x3 convolutions on 11 x 11 patches, trained by
+libmctrainmb.so (include/mc_train_mb.h) in two kernels a step, enqueued chunk by chunk through `mc_train_mb_run`.  The
+epoch loop, the augmentation draws, the permutation, the saved net and the error measure are train.py's (`draw_params`,
+`n_steps_per_epoch`, `net_fname_of`, `save_net`, `error_rate`), which were written dataset-wide.
+
+What is Middlebury's own:
+  * the image store is ragged: `x_<n>_<light>.bin` holds (n_exp, 2, 1, H_n, W_n) for light >= 2, every image with its own
+    size, number of lights and number of exposures (preprocess_mb.py).  `build_store` lays every (light, exposure, view)
+    plane into ONE flat float32 buffer with a table (offset, H, W) per plane and an index (first plane, lights, exposures)
+    per image;
+  * the left patch of a pair comes from X[img][light][exp, 1], the right ones from X[img][light_][exp_, 2], where exp_ is
+    redrawn with probability -d_exp and light_ = max(2, light - 1) with probability -d_light (main.lua:828-841):
+    `draw_sources` draws them, vectorised per chunk, and resolves them to the two plane ids of each pair;
+  * `test_te` predicts (te[i], 2) for every te, then (5, 3) and (5, 4), from light 1 of each image with that image's own
+    disp_max (meta.bin), direction -1 only, err_at 1.
+
+The draws are the reference's distributions from one numpy Generator(-seed), not Torch's Mersenne-Twister stream (see
+train.py).  `preprocess_mb.py` is not part of this project: `-data_dir` (default data.mb.<rect>_<color>) has to hold its
+output.  Not covered: -color rgb, mb slow, -a submit, -a test_all (main.lua:1136 asserts it away itself), -subset, -debug.
+"""
+import argparse
+import os
+import time
+
+import numpy as np
+
+from . import _train_mb_lib as tml
+from .binio import fromfile
+from .train import draw_params, error_rate, n_steps_per_epoch, net_fname_of, save_net
+
+CHUNK_STEPS = 256           # steps enqueued per mc_train_mb_run call (one chunk of parameter and source draws)
+ACTIONS = ("train_tr", "train_all", "test_te")
+MB_TRAIN_DEFAULTS = dict(m=0.2, pow=1, lr=0.002, bs=128, mom=0.9, true1=0.5, false1=1.5, false2=6.0, d_exp=0.2,
+                         d_light=0.2)   # main.lua:264-279
+PLANE_DTYPE = np.dtype([("offset", "<i8"), ("H", "<i4"), ("W", "<i4")])   # mc_train_mb_plane
+
+
+def parse(argv):
+    """The flags of `main.lua mb fast -a train_tr | train_all | test_te` with main.lua's names and defaults.  Returns
+    (dataset, arch, opt, prm) as main.parse does; prm has left_only = 1 (outside -a predict dataset mb runs direction -1
+    only, main.lua:953-955)."""
+    from .main import AUG_DEFAULTS
+    from .params import SM_SKIP, SM_TERMINATE, TABLES
+    if len(argv) >= 2 and argv[0] == "mb" and argv[1] == "slow":
+        raise SystemExit("train_mb: mb slow is not trained here: its net (l1 5, fm 112, l2 3) keeps 221 KB of activations per "
+                         "pair, more than the one-workgroup-per-pair step of libmctrainmb.so can hold in a CU's LDS")
+    if len(argv) < 2 or argv[0] != "mb" or argv[1] != "fast":
+        raise SystemExit("train_mb: training and testing on Middlebury cover mb fast -a %s" % " | ".join(ACTIONS))
+    t = TABLES[("mb", "fast")]
+    ap = argparse.ArgumentParser(prog="main.py mb fast", prefix_chars="-")
+    ap.add_argument("-a", required=True)
+    ap.add_argument("-net_fname", default="random:42")
+    ap.add_argument("-gpu", type=int, default=1, help="1-based, as cutorch.setDevice (main.lua:16,342)")
+    for k in ("L1", "cbca_i1", "cbca_i2", "sgm_i"):
+        ap.add_argument("-" + k, type=int, default=t[k])
+    for k in ("tau1", "pi1", "pi2", "sgm_q1", "sgm_q2", "alpha1", "tau_so", "blur_sigma", "blur_t"):
+        ap.add_argument("-" + k, type=float, default=t[k])
+    ap.add_argument("-sm_terminate", default="", choices=sorted(SM_TERMINATE), help="main.lua:25")
+    ap.add_argument("-sm_skip", default="", choices=sorted(SM_SKIP), help="main.lua:26")
+    ap.add_argument("-seed", type=int, default=42)
+    for k, v in MB_TRAIN_DEFAULTS.items():
+        ap.add_argument("-" + k, type=type(v), default=v)
+    ap.add_argument("-ds", type=int, default=2001, help="parsed and ignored: main.lua:267 declares it and never reads it")
+    for k, v in AUG_DEFAULTS["mb"].items():
+        ap.add_argument("-" + k, type=int if k in ("hflip", "vflip") else float, default=float(v) if k not in ("hflip", "vflip") else v)
+    ap.add_argument("-rect", default="imperfect", help="main.lua:68")
+    ap.add_argument("-color", default="gray", help="main.lua:69")
+    ap.add_argument("-data_dir", default="", help="default data.mb.<rect>_<color> (main.lua:456)")
+    ap.add_argument("-subset", type=float, default=1.0, help="main.lua:28; only 1 is supported")
+    ap.add_argument("-debug", action="store_true", help="main.lua:18; not supported")
+    ap.add_argument("-epochs", type=int, default=14, help="main.lua:777 runs 14")
+    ap.add_argument("-max_steps", type=int, default=0, help="stop training after this many steps in all (0: no limit)")
+    opt = ap.parse_args(argv[2:])
+    if opt.a == "test_all":
+        raise SystemExit("train_mb: -a test_all is not supported on Middlebury (main.lua:1136 asserts the same)")
+    if opt.a == "submit":
+        raise SystemExit("train_mb: -a submit is out of scope (it writes the Middlebury evaluation's PFM files)")
+    if opt.a not in ACTIONS:
+        raise SystemExit("train_mb: -a %s is not a training or testing action; mb fast covers -a %s" % (opt.a, " | ".join(ACTIONS)))
+    if opt.color != "gray":
+        raise SystemExit("train_mb: -color %s: the nets here have one input plane, only -color gray is supported" % opt.color)
+    if opt.subset != 1:
+        raise SystemExit("train_mb: -subset %g is not supported (the whole training set is used)" % opt.subset)
+    if opt.debug:
+        raise SystemExit("train_mb: -debug (main.lua:1240-1260 writes images of every prediction) is not supported")
+    if opt.bs < 2 or opt.bs % 2:
+        raise SystemExit("train_mb: -bs %d: a batch is pairs of samples (main.lua:789)" % opt.bs)
+    prm = dict(t)
+    prm["sm_terminate"], prm["sm_skip"] = opt.sm_terminate, opt.sm_skip
+    for k in ("L1", "cbca_i1", "cbca_i2", "sgm_i", "tau1", "pi1", "pi2", "sgm_q1", "sgm_q2", "alpha1", "tau_so", "blur_sigma",
+              "blur_t"):
+        prm[k] = getattr(opt, k)
+    prm["left_only"] = 1
+    return "mb", "fast", opt, prm
+
+
+def data_dir_of(opt):
+    return opt.data_dir or "data.mb.%s_%s" % (opt.rect, opt.color)
+
+
+# ---- the data ----------------------------------------------------------------------------------------------------------
+def build_store(X, need=()):
+    """X[img][light] (light 1 first) -> (planes, table, index): every (light >= 2, exposure, view) plane of every image in
+    one flat float32 buffer; table[id] = (offset in floats, H, W) (PLANE_DTYPE); index[img] = (first plane id, number of
+    lights >= 2, number of exposures).  The plane of (light, exp, view), 0-based with light 0 = the file's light 2, is
+    first + ((light * n_exp) + exp) * 2 + view.  need: 1-based image numbers that must have a light >= 2.
+    Raises ValueError, naming the image, where an image's lights differ in exposures or size (exp_ is drawn from light's
+    count and used on light_, main.lua:834-840) or a plane is outside the sampler's limits."""
+    index = np.zeros((len(X), 3), np.int64)
+    recs, total = [], 0
+    for n, lights in enumerate(X, 1):
+        tr = [np.asarray(a) for a in lights[1:]]
+        index[n - 1, 0] = len(recs)
+        if not tr:
+            if n in need:
+                raise ValueError("image %d is listed in the training nnz but has no x_%d_2.bin (no light >= 2)" % (n, n))
+            continue
+        for k, a in enumerate(tr, 2):
+            if a.ndim != 5 or a.shape[1] != 2 or a.shape[2] != 1 or a.shape[0] < 1:
+                raise ValueError("image %d: x_%d_%d.bin has shape %s, not (n_exp, 2, 1, H, W)" % (n, n, k, a.shape))
+            if a.shape != tr[0].shape:
+                raise ValueError("image %d: light %d is %s but light 2 is %s: the lights of an image must agree in exposures "
+                                 "and size" % (n, k, a.shape, tr[0].shape))
+        n_exp, H, W = tr[0].shape[0], tr[0].shape[3], tr[0].shape[4]
+        if not (tml.MIN_SIDE <= H <= tml.MAX_SIDE and tml.MIN_SIDE <= W <= tml.MAX_SIDE):
+            raise ValueError("image %d: planes of %d x %d are outside the sampler's range [%d, %d]" % (n, H, W, tml.MIN_SIDE, tml.MAX_SIDE))
+        index[n - 1, 1:] = (len(tr), n_exp)
+        for _ in range(len(tr) * n_exp * 2):
+            recs.append((total, H, W))
+            total += H * W
+    planes = np.empty(total, np.float32)
+    for n, lights in enumerate(X, 1):
+        o = recs[index[n - 1, 0]][0] if index[n - 1, 1] else 0
+        for a in lights[1:]:
+            a = np.asarray(a, np.float32)
+            planes[o:o + a.size] = a.ravel()
+            o += a.size
+    return planes, np.array(recs, PLANE_DTYPE).reshape(-1), index
+
+
+def load_mb_data(data_dir, action):
+    """main.lua:455-490: te, meta (H, W, ndisp per image), nnz_tr, nnz_te, X[img] = [x_<n>_1, x_<n>_2, ...] up to the first
+    missing light (light 1 only for test_te), dispnoc {image number: map}; for the training actions also the store
+    (planes, table, index) of build_store.  The reference appends the dispnoc files it finds to a list and indexes it by
+    image number, which is the same thing for preprocess_mb.py's sets, whose images with ground truth come first."""
+    f = lambda name: fromfile(os.path.join(data_dir, name))
+    d = dict(te=np.asarray(f("te.bin")).ravel().astype(np.int64), meta=np.asarray(f("meta.bin")).reshape(-1, 3),
+             nnz_tr=np.asarray(f("nnz_tr.bin"), np.float32).reshape(-1, 4), nnz_te=np.asarray(f("nnz_te.bin"), np.float32).reshape(-1, 4))
+    X, dispnoc = [], {}
+    for n in range(1, d["meta"].shape[0] + 1):
+        lights, light = [], 1
+        while os.path.exists(os.path.join(data_dir, "x_%d_%d.bin" % (n, light))):
+            lights.append(f("x_%d_%d.bin" % (n, light)))
+            light += 1
+            if action == "test_te":
+                break                      # main.lua:479-481: the training data is not needed
+        X.append(lights)
+        if os.path.exists(os.path.join(data_dir, "dispnoc%d.bin" % n)):
+            dispnoc[n] = f("dispnoc%d.bin" % n)
+    d["X"], d["dispnoc"] = X, dispnoc
+    if action != "test_te":
+        nnz = d["nnz_tr"] if action == "train_tr" else np.concatenate([d["nnz_tr"], d["nnz_te"]], 0)
+        need = set(int(v) for v in np.unique(nnz[:, 0]))
+        bad = [n for n in need if not 1 <= n <= len(X)]
+        if bad:
+            raise ValueError("%s: the nnz lists image %d, meta.bin has %d images" % (data_dir, bad[0], len(X)))
+        try:
+            d["planes"], d["table"], d["index"] = build_store(X, need)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (data_dir, e)) from None
+    return d
+
+
+def draw_sources(rng, opt, img_ids, index):
+    """main.lua:829-840 for pairs of images img_ids (1-based, any shape): light uniform over the image's lights >= 2, exp
+    uniform over its exposures, exp_ = exp redrawn uniformly with probability d_exp, light_ = light or, with
+    probability d_light, max(2, light - 1).  Returns the plane ids, int32 of shape img_ids.shape + (2,): [..., 0] the
+    left view of (light, exp), [..., 1] the right view of (light_, exp_)."""
+    img = np.asarray(img_ids).astype(np.int64) - 1
+    first, n_light, n_exp = index[img, 0], index[img, 1], index[img, 2]
+    if (n_light < 1).any():
+        raise ValueError("draw_sources: image %d has no light >= 2" % (int(img[n_light < 1].ravel()[0]) + 1))
+    light = rng.integers(0, n_light)           # 0 is the file's light 2
+    exp = rng.integers(0, n_exp)
+    exp_ = np.where(rng.uniform(0, 1, img.shape) < opt.d_exp, rng.integers(0, n_exp), exp)
+    light_ = np.where(rng.uniform(0, 1, img.shape) < opt.d_light, np.maximum(0, light - 1), light)
+    return np.stack([first + (light * n_exp + exp) * 2, first + (light_ * n_exp + exp_) * 2 + 1], -1).astype(np.int32)
+
+
+# ---- the net's parameters ----------------------------------------------------------------------------------------------
+def flat_params(layers):
+    """[(w, b)] of the five-layer net -> one float32 vector in include/mc_train_mb.h's order (w1 b1 .. w5 b5)."""
+    layers = list(layers)
+    want = [(tml.FM, 1 if i == 0 else tml.FM, 3, 3) for i in range(tml.L1)]
+    if [tuple(np.shape(w)) for w, _ in layers] != want or [tuple(np.shape(b)) for _, b in layers] != [(tml.FM,)] * tml.L1:
+        raise ValueError("net of shapes %s, libmctrainmb.so trains l1 5, fm 64 on 1 input plane" % ([tuple(np.shape(w)) for w, _ in layers],))
+    return np.concatenate([np.asarray(a, np.float32).ravel() for wb in layers for a in wb])
+
+
+def unflat_params(v):
+    v = np.asarray(v, np.float32)
+    if v.size != tml.NPARAMS:
+        raise ValueError("%d floats, Middlebury's fast net has %d" % (v.size, tml.NPARAMS))
+    layers, o = [], 0
+    for i in range(tml.L1):
+        cin = 1 if i == 0 else tml.FM
+        n = tml.FM * cin * 9
+        layers.append((v[o:o + n].reshape(tml.FM, cin, 3, 3).copy(), v[o + n:o + n + tml.FM].copy()))
+        o += n + tml.FM
+    return layers
+
+
+# ---- the device side -----------------------------------------------------------------------------------------------------
+def _p(t):
+    return t.data_ptr()
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def device_table(table, device):
+    """PLANE_DTYPE records -> the device tensor mc_train_mb_* take (two int64 words per record)."""
+    import torch
+    table = np.ascontiguousarray(table, PLANE_DTYPE)
+    bad = (table["H"] < tml.MIN_SIDE) | (table["W"] < tml.MIN_SIDE) | (table["H"] > tml.MAX_SIDE) | (table["W"] > tml.MAX_SIDE)
+    if bad.any():
+        k = int(np.nonzero(bad)[0][0])
+        raise ValueError("plane %d of %d x %d is outside the sampler's range [%d, %d]" % (k, table["H"][k], table["W"][k], tml.MIN_SIDE,
+                                                                                         tml.MAX_SIDE))
+    return torch.from_numpy(table.view(np.int64).reshape(-1, 2).copy()).to(device)
+
+
+class Trainer:
+    """Device state of a training run: planes, table, nnz, permutation, parameters, momenta, workspace."""
+
+    def __init__(self, planes, table, nnz, perm, layers, n_pairs, device):
+        import torch
+        self.lib = tml.load()
+        self.dev = device
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
+        self.table = device_table(table, device)
+        self.planes = f32(planes)
+        self.nnz = f32(np.asarray(nnz).reshape(-1, 4))
+        self.perm = torch.from_numpy(np.ascontiguousarray(perm, np.int32)).to(device)
+        self.params = f32(flat_params(layers))
+        self.moms = torch.zeros_like(self.params)
+        self.n_pairs = n_pairs
+        self.ws_bytes = self.lib.mc_train_mb_workspace_bytes(n_pairs)
+        if self.ws_bytes == 0:
+            raise ValueError("train_mb: %d pairs per batch is outside libmctrainmb.so's range [1, %d]" % (n_pairs, tml.MAX_PAIRS))
+        self.ws = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=device)
+
+    def run(self, t0, src, prm, lr, mom, margin, pow_, losses):
+        """mc_train_mb_run: src (n_steps, n_pairs, 2) int32 and prm (n_steps, n_pairs, 18) on the device; losses
+        (>= n_steps) device float32."""
+        n_steps = prm.shape[0]
+        assert tuple(src.shape) == (n_steps, self.n_pairs, 2) and tuple(prm.shape) == (n_steps, self.n_pairs, tml.NPRM)
+        tml.check(self.lib.mc_train_mb_run(_p(self.planes), _p(self.table), self.table.shape[0], _p(self.nnz), self.nnz.shape[0],
+                                           _p(self.perm), self.perm.shape[0], t0, n_steps, self.n_pairs, _p(src), _p(prm),
+                                           _p(self.params), _p(self.moms), lr, mom, margin, pow_, _p(losses), self.ws.data_ptr(),
+                                           self.ws_bytes, _stream()), "mc_train_mb_run")
+
+    def layers(self):
+        return unflat_params(self.params.cpu().numpy())
+
+
+def sample(planes, table, nnz, rows, src, prm):
+    """mc_train_mb_sample on device tensors: planes (flat), table (device_table's), nnz (n, 4), rows (n_pairs,) int32,
+    src (n_pairs, 2) int32, prm (n_pairs, 18) -> (n_pairs, 3, 11, 11): left, positive, negative patch of each pair."""
+    import torch
+    lib = tml.load()
+    out = torch.empty((rows.shape[0], 3, tml.WS, tml.WS), dtype=torch.float32, device=planes.device)
+    tml.check(lib.mc_train_mb_sample(_p(planes), _p(table), table.shape[0], _p(nnz), nnz.shape[0], _p(rows), _p(src), _p(prm),
+                                     rows.shape[0], _p(out), _stream()), "mc_train_mb_sample")
+    return out
+
+
+def step_batch(patches, params, moms, lr, mom, margin, pow_, workspace=None):
+    """mc_train_mb_step_batch: one SGD step on patches (n_pairs, 3, 11, 11); params / moms (148352,) updated in place.
+    Returns the device scalar of the batch's mean loss."""
+    import torch
+    lib = tml.load()
+    n_pairs = patches.shape[0]
+    if workspace is None:
+        workspace = torch.empty(lib.mc_train_mb_workspace_bytes(n_pairs) // 4, dtype=torch.float32, device=patches.device)
+    loss = torch.empty(1, dtype=torch.float32, device=patches.device)
+    tml.check(lib.mc_train_mb_step_batch(_p(patches), n_pairs, _p(params), _p(moms), lr, mom, margin, pow_, _p(loss),
+                                         workspace.data_ptr(), workspace.numel() * 4, _stream()), "mc_train_mb_step_batch")
+    return loss
+
+
+# ---- training and testing ------------------------------------------------------------------------------------------------
+last_run = None   # the latest train() result: {"net_fname", "losses" (per step, float32), "epochs"}
+
+
+def train(opt, argv, device, data=None):
+    """main.lua:602-890 for mb fast, -a train_tr / train_all: returns the saved net's file name.  The loop is
+    train.train's (one permutation, drawn once; chunks of CHUNK_STEPS steps; lr / 10 from epoch 12; -max_steps), with the
+    pairs' sources drawn beside their augmentation parameters."""
+    global last_run
+    import torch
+    from .main import load_net
+    if data is None:
+        data = load_mb_data(data_dir_of(opt), opt.a)
+    nnz = data["nnz_tr"] if opt.a == "train_tr" else np.concatenate([data["nnz_tr"], data["nnz_te"]], 0)
+    nnz = np.asarray(nnz, np.float32).reshape(-1, 4)
+    n_pairs = opt.bs // 2
+    rng = np.random.default_rng(opt.seed)
+    perm = rng.permutation(nnz.shape[0]).astype(np.int32)
+    img_of = nnz[perm, 0].astype(np.int64)      # the image of every pair of an epoch, in the permutation's order
+    layers = load_net("random:%d" % opt.seed, "mb", "fast")
+    tr = Trainer(data["planes"], data["table"], nnz, perm, layers, n_pairs, device)
+    steps = n_steps_per_epoch(nnz.shape[0], opt.bs)
+    if steps < 1:
+        raise SystemExit("train: %d training pairs, fewer than a batch of %d" % (nnz.shape[0], n_pairs))
+    budget = opt.max_steps if opt.max_steps > 0 else None
+    lr = opt.lr
+    all_losses = []
+    t_start = time.perf_counter()
+    losses = torch.empty(steps, dtype=torch.float32, device=device)
+    for epoch in range(1, opt.epochs + 1):
+        if budget is not None and budget <= 0:
+            break
+        if epoch == 12:
+            lr = lr / 10
+        n = steps if budget is None else min(steps, budget)
+        for s0 in range(0, n, CHUNK_STEPS):
+            k = min(CHUNK_STEPS, n - s0)
+            prm = torch.from_numpy(draw_params(rng, opt, k, n_pairs)).to(device)
+            ids = img_of[s0 * n_pairs:(s0 + k) * n_pairs].reshape(k, n_pairs)
+            src = torch.from_numpy(draw_sources(rng, opt, ids, data["index"])).to(device)
+            tr.run(s0 * n_pairs, src, prm, lr, opt.mom, opt.m, opt.pow, losses[s0:])
+        ep = losses[:n].cpu().numpy().copy()   # synchronises: the epoch's steps are done
+        all_losses.append(ep)
+        ok = (ep >= 0) & (ep < 100)           # main.lua:861-866
+        for e in ep[~ok]:
+            print("WARNING! err=%f" % e)
+        print(epoch, float(ep[ok].mean()) if ok.any() else float("nan"), lr, time.perf_counter() - t_start)
+        if budget is not None:
+            budget -= n
+    opt.lr = lr
+    fname = save_net(net_fname_of("mb", "fast", argv), tr.layers(), opt)
+    last_run = {"net_fname": fname, "losses": np.concatenate(all_losses) if all_losses else np.zeros(0, np.float32),
+                "epochs": len(all_losses)}
+    return fname
+
+
+def test_examples(te):
+    """main.lua:1124-1130: (te[i], 2) for every te, then (5, 3) and (5, 4): (image number, 1-based view of light 1)."""
+    return [(int(i), 2) for i in np.asarray(te).ravel()] + [(5, 3), (5, 4)]
+
+
+def evaluate(opt, prm, run, device, data=None):
+    """main.lua:1172-1238, 1290-1292 for mb test_te: predict each example through `run(x_batch, D, workspace=...)` with the
+    image's own disp_max, print `runtime err` per example (err_at 1, against dispnoc) and the mean error.  Returns the
+    mean."""
+    import torch
+    from .predict import Workspace
+    if data is None:
+        data = load_mb_data(data_dir_of(opt), "test_te")
+    err_at = 1
+    errs, shape, ws = [], None, None     # one Workspace per shape; consecutive examples of one image share theirs
+    for i, right in test_examples(data["te"]):
+        if not 1 <= i <= len(data["X"]) or not data["X"][i - 1] or np.asarray(data["X"][i - 1][0]).ndim != 4:
+            raise SystemExit("test_te: image %d has no test views (x_%d_1.bin is missing or empty)" % (i, i))
+        x = np.asarray(data["X"][i - 1][0], np.float32)
+        if right > x.shape[0]:
+            raise SystemExit("test_te: image %d has %d test views, view %d is asked for" % (i, x.shape[0], right))
+        if i not in data["dispnoc"]:
+            raise SystemExit("test_te: image %d has no dispnoc%d.bin" % (i, i))
+        D = int(data["meta"][i - 1, 2])
+        if D <= 0:
+            raise SystemExit("test_te: meta.bin gives image %d a disp_max of %d" % (i, D))
+        H, W = x.shape[-2:]
+        xb = torch.from_numpy(np.ascontiguousarray(np.stack([x[0], x[right - 1]]).reshape(2, 1, H, W))).to(device)
+        if (D, H, W) != shape:
+            ws = None                          # release the previous shape's before taking the next
+            shape, ws = (D, H, W), Workspace(prm, D, H, W, device)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pred = run(xb, D, workspace=ws)["disp"]
+        torch.cuda.synchronize()
+        runtime = time.perf_counter() - t0
+        pred = pred.cpu().numpy().reshape(H, W)
+        assert not np.isnan(pred.sum())
+        err = error_rate(pred, np.asarray(data["dispnoc"][i], np.float32).reshape(H, W), err_at)
+        errs.append(err)
+        print(runtime, err)
+    mean = sum(errs) / len(errs)
+    print(mean)
+    return mean

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Which of the kernels of libmcadcensus.so and libmctrain.so a profiled run launched.
 
-    scripts/kernel_coverage.py KERNEL_STATS_CSV [KERNEL_STATS_CSV ...] [--inventory FILE ...]   (default: both inventory files under tests/)
+    scripts/kernel_coverage.py KERNEL_STATS_CSV [KERNEL_STATS_CSV ...] [--inventory FILE ...]   (default: the inventory files under tests/)
 
 Reads the kernel_stats.csv files that `rocprofv3 --kernel-trace --stats` writes (e.g. for `pytest tests -m gpu`), normalises the
 kernel names the way tests/kernel_inventory.txt lists them, and prints the inventory kernels the run never launched and the
@@ -21,6 +21,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVENTORY = os.path.join(ROOT, "tests", "kernel_inventory.txt")
 INVENTORY_TRAIN_SLOW = os.path.join(ROOT, "tests", "kernel_inventory_train_slow.txt")   # libmctrainslow.so
+INVENTORY_TRAIN_MB = os.path.join(ROOT, "tests", "kernel_inventory_train_mb.txt")       # libmctrainmb.so
 NAMESPACE = "mc::"
 
 
@@ -82,7 +83,7 @@ def launched(csv_paths):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("stats", nargs="+", help="kernel_stats.csv of rocprofv3 --kernel-trace --stats")
-    ap.add_argument("--inventory", nargs="+", default=[INVENTORY, INVENTORY_TRAIN_SLOW])
+    ap.add_argument("--inventory", nargs="+", default=[INVENTORY, INVENTORY_TRAIN_SLOW, INVENTORY_TRAIN_MB])
     a = ap.parse_args(argv)
     inv = {}
     for path in a.inventory:

@@ -291,7 +291,7 @@ int mc_sgm2(const float *x0, const float *x1, const float *in_hwd, float *out_hw
 	const float *Cv[2] = {in_hwd, in_hwd};
 	float *outv[2] = {out_hwd, out_hwd};
 	const int dirv[2] = {direction, direction};
-	return sgm_sweeps(Cv, outv, nullptr, nullptr, dirv, 1, H, W, D, D, tmp, pi1, pi2, alpha1, sgm_q1, sgm_q2, false, 0u, st);
+	return sgm_sweeps(Cv, outv, nullptr, nullptr, dirv, 1, H, W, D, D, tmp, pi1, pi2, alpha1, sgm_q1, sgm_q2, false, 0u, false, st);
 }
 
 int mc_dhw_to_hwd(const float *in, float *out, int D, int H, int W, void *stream)

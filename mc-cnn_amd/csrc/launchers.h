@@ -71,7 +71,7 @@ int sgm_prep(const float *x0, const float *x1, void *maps, int H, int W, float t
 int sgm_contract_violations(const float *vol, int H, int W, int D, unsigned *count, hipStream_t st);
 int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
                const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,
-               float alpha1, float q1, float q2, bool fused, unsigned drop_final, hipStream_t st);
+               float alpha1, float q1, float q2, bool fused, unsigned drop_final, bool tri, hipStream_t st);
 
 // predict.hip
 static inline int gaussian_ks(double sigma) { return 2 * (int)ceil(sigma * 3) + 1; }   // main.lua:529-530

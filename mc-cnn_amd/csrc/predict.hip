@@ -218,11 +218,18 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	// (C + 64: the kernels pad the channel count to their k-step sizes and add channel offsets to range-checked 32-bit byte
 	// offsets -- no padded channel's offset may wrap)
 	const bool join_fits = (int64_t)W * ((D + 3) / 4 * 4) * 4 < ((int64_t)1 << 31) && ((int64_t)(C + 64) * HW + W) * 4 < ((int64_t)1 << 31);
+	// the volumes hold NaN wherever the partner pixel lies outside the image (left: d > x, right: x + d >= W), sgm_sweeps' `tri`
+	bool nan_triangle = false;
 	if (from_feat && n_cbca1 == 0 && n_sgm > 0 && join_fits) {
 		// fast path: StereoJoin straight into (H,W,ds) with NaN fill and fix_border folded in
 		RUN(stereo_join_hwd(featL, featR, pl.bufA[0], pl.bufA[1], C, D, ds, H, W, p->border_n, st));
 		cur[0] = pl.bufA[0]; cur[1] = pl.bufA[1];
 		hwd = true;
+		// stereo_join_hwd writes NaN there itself.  Its fix_border_hwd then copies the whole cost vector of column W - (n + 1) to the
+		// columns right of it (left volume) and of column n to the columns left of it (right volume): the source column has no more
+		// live disparities than any target (x + 1 grows to the right, W - x to the left), so the copy may add NaNs below a
+		// target's Dv but leaves none out at or above it.  Every SGM iteration keeps the triangle NaN (NaN + anything).
+		nan_triangle = true;
 		tm.mark(MC_STAGE_JOIN);
 	} else {
 		if (from_feat) {  // main.lua:946-949
@@ -264,7 +271,7 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 			// left volume, the LR check the arg-min maps that the up sweep writes regardless) -- not stored unless asked for
 			const unsigned drop_final = (am && nvol == 2 && !volR_out) ? 2u : 0u;
 			RUN(sgm_sweeps(Cv, outv, pl.bufC, am ? dispv : nullptr, direction, nvol, H, W, D, ds, pl.maps, p->pi1, p->pi2, p->alpha1,
-			               p->sgm_q1, p->sgm_q2, true, drop_final, st));
+			               p->sgm_q1, p->sgm_q2, true, drop_final, nan_triangle, st));
 			have_disp = am;
 			cur[0] = outv[0]; cur[1] = outv[1];
 		}

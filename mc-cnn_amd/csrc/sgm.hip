@@ -41,6 +41,8 @@ struct SgmPassArgs {
 	int direction[2];
 	int nvol;
 	int H, W, D, ds;
+	int tri;              // 1: the caller's promise about the volumes' NaN triangle (sgm_sweeps): the vertical fused sweeps leave it alone
+	                      // (in the padding in front of cls0: every other field keeps its offset, and the other instances their code)
 	const uint8_t *cls0;  // [4][cls_plane], plane = H*W bytes padded to a dword multiple
 	int64_t cls_plane;
 	const uint8_t *win;   // [2][4][H][Wm]
@@ -197,6 +199,15 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 	const int woff = (direction > 0 ? dbase : -dbase - 3) + WBIAS;
 	const int wq = direction > 0 ? 4 : -4;
 	const int run_bytes = (VEC ? ds : D) * 4;
+	// The NaN triangle (A.tri, the fused vertical sweeps only): a vertical line is one image column x, and C is NaN in that column at
+	// every d >= Dv = min(D, x + 1) (left volume, direction -1) or min(D, W - x) (right volume) -- so are accin and accin2, and so
+	// is what this sweep would store there.  The lanes at d >= Dv neither load nor store: they get the out-of-range offset below, the
+	// recurrence gives them +INF by the select (before: vmin2(NaN, INF)), the arg-min leaves them out.  Dv is wave-uniform and
+	// loop-invariant; a 16-byte piece that straddles Dv is moved whole (its upper values are NaN in memory and stay NaN).
+	constexpr bool TRI = DIRN >= 2 && MODE >= 2;
+	int Dv = D;
+	if (TRI && A.tri) Dv = __builtin_amdgcn_readfirstlane(min(D, direction < 0 ? line + 1 : W - line));
+	const unsigned live_bytes = (TRI && Dv < D) ? (unsigned)Dv * 4u : (unsigned)run_bytes;
 
 	const float INF = __builtin_inff();
 	// the nine penalties live in SGPRs for the whole sweep
@@ -229,7 +240,8 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 #pragma unroll
 	for (int q = 0; q < (VEC ? VPL / 4 : VPL); ++q) {
 		const unsigned b = (unsigned)(dbase + (VEC ? 4 * q : q)) * 4u;
-		lane_off[q] = (FAR || b < (unsigned)run_bytes) ? b : OOBV;
+		// (FAR: the per-pixel descriptor of run_bytes checks the run's end itself; OOBV lies beyond it too)
+		lane_off[q] = ((FAR && !TRI) || b < live_bytes) ? b : OOBV;
 	}
 	const unsigned lane0_off = lane == 0 ? 0u : OOBV;
 
@@ -287,7 +299,7 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 			int bi = 0;
 #pragma unroll
 			for (int j = 0; j < VPL; ++j) {
-				if (dbase + j < D && o[j] < best) {
+				if (dbase + j < Dv && o[j] < best) {
 					best = o[j];
 					bi = dbase + j;
 				}
@@ -364,7 +376,7 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 			q[j] = vmin2(val[j], INFv);                       // NaN -> +INF: fminf semantics of the recurrence
 		}
 #pragma unroll
-		for (int j = 0; j < VPL; ++j) prev[j] = (dbase + j < D) ? q[j] : INFv;
+		for (int j = 0; j < VPL; ++j) prev[j] = (dbase + j < Dv) ? q[j] : INFv;
 		float nm = vmin3(prev[0], prev[1], prev[2]);
 #pragma unroll
 		for (int j = 3; j < VPL; j += 2) nm = j + 1 < VPL ? vmin3(nm, prev[j], prev[j + 1]) : vmin2(nm, prev[j]);
@@ -530,9 +542,15 @@ static void launch_pass(const SgmPassArgs &A, bool vec, hipStream_t st)
 //                  ds % 4 == 0 and every volume 16-byte aligned (required: mc_predict's workspace).
 //                  Bit v of drop_final (fused only): the up sweep does not store volume v's final costs -- out[v] is
 //                  left as the down sweep wrote it, the arg-min disp[v] is written as before.
+//                  tri (fused only) is the caller's promise that, for every volume v, C[v] is NaN at every (pixel, d) with
+//                  d >= Dv, Dv = min(D, x + 1) for direction[v] < 0 and min(D, W - x) for direction[v] > 0 (the voxels whose
+//                  partner pixel lies outside the image).  The horizontal launch then writes NaN there into out and out2, and the
+//                  two vertical launches, which work in place on out, neither read nor write those voxels: every buffer
+//                  holds what it holds without the promise, except the padding d in [D, ds) of a trimmed column, which
+//                  keeps the horizontal launch's values (nothing reads the padding).
 int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
                const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,
-               float alpha1, float q1, float q2, bool fused, unsigned drop_final, hipStream_t st)
+               float alpha1, float q1, float q2, bool fused, unsigned drop_final, bool tri, hipStream_t st)
 {
 	// 32-bit pixel indices and line strides in the sweeps (a volume may still exceed 4 GiB: the FAR instances)
 	MC_REQUIRE((int64_t)H * W < ((int64_t)1 << 29) && (int64_t)W * ds * 4 < ((int64_t)1 << 31), "sgm: image %dx%d (pixel stride %d) exceeds the sweeps' 32-bit line arithmetic", H, W, ds);
@@ -549,6 +567,7 @@ int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2
 		A.drop_out[v] = 0;
 	}
 	A.nvol = nvol;
+	A.tri = (fused && tri) ? 1 : 0;
 	A.H = H; A.W = W; A.D = D; A.ds = ds;
 	const SgmMaps m = sgm_maps(H, W);
 	A.Wm = m.Wm;

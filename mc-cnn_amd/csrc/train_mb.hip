@@ -22,7 +22,7 @@
 // K is split over four waves where a GEMM has only two output tiles: forward of layers 4 and 5, data gradient of layer 5.
 #include "mc_common.h"
 #include "../../include/mc_train_mb.h"
-#include "train_sampler.h"
+#include "train_mb_sampler.h"   // sample_mb_pixel: a pair's patches from the ragged store, shared with train_mb_slow.hip
 #include "train_conv.h"
 
 namespace mc {
@@ -54,28 +54,6 @@ constexpr size_t STEP_LDS_BYTES = (size_t)L_TOTAL * sizeof(float);
 static_assert(NPIX <= L_A1 && NPIX <= NT, "the patches' slot, one thread per patch pixel");
 static_assert(STEP_LDS_BYTES == 161024 && STEP_LDS_BYTES <= 160 * 1024, "a CU has 160 KiB of LDS");
 
-// Pixel t (0 .. 3*121-1) of a pair's three patches: the left one from plane src[0], both right ones from plane src[1], centred
-// by nnz row `row`.  A row outside nnz or a plane id outside the table reads 0: the warp's result is 0, then * contrast +
-// brightness like any patch that lies outside its image.  A record the sampler could not address (a side below 4 or of
-// 32768 and more; the loader refuses them) counts as outside the table.
-__device__ float sample_mb_pixel(const float *__restrict__ planes, const mc_train_mb_plane *__restrict__ table, int n_planes,
-                                 const float *__restrict__ nnz, int64_t n_nnz, int row, const int32_t *__restrict__ src,
-                                 const float *__restrict__ prm, int t)
-{
-	const int patch = t / (PS * PS), pix = t - patch * PS * PS;
-	float p[8];
-	for (int k = 0; k < 8; ++k) p[k] = prm[(patch == 0 ? 2 : 10) + k];
-	if (row < 0 || row >= n_nnz) return 0.f * p[7] + p[6];
-	const int id = src[patch == 0 ? 0 : 1];
-	if (id < 0 || id >= n_planes) return 0.f * p[7] + p[6];
-	const mc_train_mb_plane pl = table[id];
-	if (pl.H < 4 || pl.W < 4 || pl.H >= 32768 || pl.W >= 32768) return 0.f * p[7] + p[6];
-	const float *z = nnz + (int64_t)row * 4;
-	const double dim3 = z[1], dim4 = z[2], d = z[3];
-	const double col = patch == 0 ? dim4 : dim4 - d + (double)prm[patch == 1 ? 0 : 1];
-	return sample_pixel<PS>(planes + pl.offset, pl.H, pl.W, dim3, col, p, pix % PS, pix / PS);
-}
-
 __global__ void __launch_bounds__(384) train_mb_sample_kernel(const float *__restrict__ planes, const mc_train_mb_plane *__restrict__ table,
                                                               int n_planes, const float *__restrict__ nnz, int64_t n_nnz,
                                                               const int32_t *__restrict__ rows, const int32_t *__restrict__ src,
@@ -83,8 +61,8 @@ __global__ void __launch_bounds__(384) train_mb_sample_kernel(const float *__res
 {
 	const int pair = blockIdx.x, t = threadIdx.x;
 	if (t < NPIX)
-		out[(int64_t)pair * NPIX + t] = sample_mb_pixel(planes, table, n_planes, nnz, n_nnz, rows[pair], src + 2 * (int64_t)pair,
-		                                                prm + (int64_t)pair * NPRM, t);
+		out[(int64_t)pair * NPIX + t] = sample_mb_pixel<PS>(planes, table, n_planes, nnz, n_nnz, rows[pair], src + 2 * (int64_t)pair,
+		                                                    prm + (int64_t)pair * NPRM, t);
 }
 
 // Kernel (a): one workgroup per pair.  SAMPLE: the patches come from the planes (rows[pair] of nnz, src and prm of the
@@ -102,7 +80,7 @@ __global__ void __launch_bounds__(NT) train_mb_step_kernel(const float *__restri
 	float *X = lds + L_X, *A1 = lds + L_A1, *A2 = lds + L_A2, *A3 = lds + L_A3, *A4 = lds + L_A4, *A5 = lds + L_A5, *split = lds + L_SPLIT;
 	if (t < NPIX) {
 		if (SAMPLE)
-			X[t] = sample_mb_pixel(planes, table, n_planes, nnz, n_nnz, rows[pair], src + 2 * (int64_t)pair, prm + (int64_t)pair * NPRM, t);
+			X[t] = sample_mb_pixel<PS>(planes, table, n_planes, nnz, n_nnz, rows[pair], src + 2 * (int64_t)pair, prm + (int64_t)pair * NPRM, t);
 		else
 			X[t] = patches[(int64_t)pair * NPIX + t];
 	}

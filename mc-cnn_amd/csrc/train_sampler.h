@@ -1,6 +1,6 @@
-// The patch sampler of the training libraries (libmctrain.so, libmctrainslow.so, libmctrainmb.so): one device function,
+// The patch sampler of the training libraries (libmctrain.so, libmctrainslow.so, libmctrainmb.so, libmctrainmbslow.so): one device function,
 // so that all draw the same patches bit for bit.  The patch size PS is a template parameter: 9 for the KITTI nets (WS), 11 for
-// Middlebury's five-layer net.
+// Middlebury's two five-layer nets.
 #pragma once
 #include "mc_common.h"
 #include "../../include/mc_train.h"

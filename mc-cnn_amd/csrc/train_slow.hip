@@ -20,25 +20,27 @@
 //                              v = mom * v - lr * g;  w += v  to all 870 449 parameters
 // The launch count is above the ~10 the design aimed for: the four hidden Linears' forward and backward GEMMs each need
 // the whole previous layer, and a device-wide barrier inside one kernel was not worth its risk.
+// The GEMMs of the towers are train_slow_conv.h's, the FC kernels and the update train_slow_fc.h's: both are shared with
+// train_mb_slow.hip (Middlebury's accurate net, one patch per workgroup).  This file holds the layer chain, the LDS layout, the
+// workspace and the entry points.
 #include "mc_common.h"
 #include "../../include/mc_train_slow.h"
 #include "train_sampler.h"
+#include "train_slow_conv.h"   // block_gemm and the three convolution GEMMs, here with a pair's three patches per workgroup
+#define MC_FC_HEAD_MAX_ROWS (2 * MC_TRAIN_SLOW_MAX_PAIRS)
+#include "train_slow_fc.h"     // fc_forward_kernel, fc_head_kernel, fc_backward_kernel, sgd_update
 
 namespace mc {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-constexpr int FM = MC_TRAIN_SLOW_FM;
-constexpr int NH = MC_TRAIN_SLOW_NH2;
 constexpr int NIN = 2 * FM;              // columns of the FC stack's input
 constexpr int NPRM = MC_TRAIN_SLOW_NPRM;
 constexpr int NCONV = MC_TRAIN_SLOW_NCONV;
 constexpr int NFC = MC_TRAIN_SLOW_NFC;
 constexpr int NPARAMS = MC_TRAIN_SLOW_NPARAMS;
-constexpr int NW = 8;                    // waves per tower workgroup (two per SIMD)
-constexpr int NT = NW * 64;
+constexpr int NP = 3;                    // patches per tower workgroup: a pair's
 constexpr int NPIX = 3 * WS * WS;        // floats of a pair's patches
 static_assert(MC_TRAIN_SLOW_WS == WS && MC_TRAIN_SLOW_NPRM == MC_TRAIN_NPRM, "the sampler's patch and parameter layout");
+static_assert(FM == MC_TRAIN_SLOW_FM && NH == MC_TRAIN_SLOW_NH2, "train_slow_conv.h's feature maps, train_slow_fc.h's hidden units");
 static_assert(FM % 16 == 0 && NH % 16 == 0 && NIN % 16 == 0, "16 x 16 tiles");
 
 // offsets of the flat parameter buffer: w1 b1 w2 b2 w3 b3 w4 b4 | fw1 fb1 .. fw4 fb4 fw5 fb5
@@ -63,137 +65,17 @@ constexpr int L_TOTAL = L_A4 + 3 * FM;
 constexpr size_t TOWER_LDS_BYTES = (size_t)L_TOTAL * sizeof(float);
 static_assert(TOWER_LDS_BYTES <= 160 * 1024, "one pair's activations fit a CU's LDS");
 
-__device__ __forceinline__ floatx4 mfma(float a, float b, floatx4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// ---- the tower: block GEMMs of (M = 112) x N over the workgroup's waves ------------------------------------------------
-// Tiles of 16 x 16; a lane holds A[row lane&15][k = lane>>4] and B[k = lane>>4][col lane&15]; its result register r is row
-// 4 * (lane>>4) + r of column lane&15.
-// mac(acc, i, j, kg): every K step for output row i / column j on lane group kg.  out(row, col, v): one element's epilogue.
-template <class Mac, class Out>
-__device__ __forceinline__ void block_gemm(int N, Mac mac, Out out)
-{
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kg = lane >> 4, l = lane & 15;
-	const int ntile = (FM / 16) * ((N + 15) / 16);
-	for (int task = wave; task < ntile; task += NW) {
-		const int mt = task % (FM / 16), nt = task / (FM / 16);
-		floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-		mac(acc, mt * 16 + l, nt * 16 + l, kg);
-		const int col = nt * 16 + l;
-		if (col < N)
-			for (int r = 0; r < 4; ++r) out(mt * 16 + 4 * kg + r, col, acc[r]);
-	}
-}
-
-// forward of a layer with CIN input maps of SI x SI per patch into FM maps of (SI-2)^2: out = ReLU(b + W * in)
-template <int CIN, int SI>
-__device__ void conv_forward(const float *__restrict__ w, const float *__restrict__ bias, const float *in, float *out)
-{
-	constexpr int SO = SI - 2, PO = SO * SO, PI = SI * SI, N = 3 * PO;
-	auto mac = [&](floatx4 &acc, int i, int j, int kg) {
-		const int jc = j < N ? j : N - 1;
-		const int patch = jc / PO, pix = jc - patch * PO, py = pix / SO, px = pix - py * SO;
-		const float *pb = in + patch * CIN * PI + py * SI + px;
-		if constexpr (CIN == 1) {
-			for (int s = 0; s < 3; ++s) {
-				const int tap = 4 * s + kg;
-				const float a = tap < 9 ? w[i * 9 + tap] : 0.f;
-				const float b = tap < 9 ? pb[(tap / 3) * SI + tap % 3] : 0.f;
-				acc = mfma(a, b, acc);
-			}
-		} else {
-			const float *pa = w + i * CIN * 9 + kg * 9;
-			pb += kg * PI;
-			for (int s = 0; s < CIN / 4; ++s, pa += 36, pb += 4 * PI) {
-				float a[9];
-#pragma unroll
-				for (int t = 0; t < 9; ++t) a[t] = pa[t];
-#pragma unroll
-				for (int t = 0; t < 9; ++t) acc = mfma(a[t], pb[(t / 3) * SI + t % 3], acc);
-			}
-		}
-	};
-	auto put = [&](int co, int j, float v) {
-		const int patch = j / PO, pix = j - patch * PO;
-		out[(patch * FM + co) * PO + pix] = fmaxf(v + bias[co], 0.f);
-	};
-	block_gemm(N, mac, put);
-}
-
-// weight and bias gradients of a layer: dW[co, ci, tap] = sum_p g[co, p] in[ci, p + tap] into the pair's slab row
-template <int CIN, int SI>
-__device__ void conv_weight_grad(const float *g, const float *in, float *__restrict__ dw, float *__restrict__ db)
-{
-	constexpr int SO = SI - 2, PO = SO * SO, PI = SI * SI, P = 3 * PO, KN = CIN * 9;
-	auto mac = [&](floatx4 &acc, int i, int j, int kg) {
-		const int jc = j < KN ? j : KN - 1;
-		const int ci = jc / 9, tap = jc - ci * 9;
-		const float *pb = in + ci * PI + (tap / 3) * SI + tap % 3;
-		const float *pa = g + i * PO;
-		for (int s = 0; s < (P + 3) / 4; ++s) {
-			const int p = 4 * s + kg;
-			const int pc = p < P ? p : P - 1;
-			const int patch = pc / PO, pix = pc - patch * PO, py = pix / SO, px = pix - py * SO;
-			const float a = p < P ? pa[patch * FM * PO + pix] : 0.f;
-			const float b = p < P ? pb[patch * CIN * PI + py * SI + px] : 0.f;
-			acc = mfma(a, b, acc);
-		}
-	};
-	auto put = [&](int co, int j, float v) { dw[co * KN + j] = v; };
-	block_gemm(KN, mac, put);
-	if (threadIdx.x < FM) {
-		const int co = threadIdx.x;
-		float s = 0.f;
-		for (int patch = 0; patch < 3; ++patch)
-			for (int pix = 0; pix < PO; ++pix) s += g[(patch * FM + co) * PO + pix];
-		db[co] = s;
-	}
-}
-
-// data gradient of a layer into its input activations, in place, masked by their ReLU: in[ci, q] = in > 0 ? dX : 0
-template <int SI>
-__device__ void conv_data_grad(const float *__restrict__ w, const float *g, float *in)
-{
-	constexpr int SO = SI - 2, PO = SO * SO, PI = SI * SI, N = 3 * PI;
-	auto mac = [&](floatx4 &acc, int i, int j, int kg) {
-		const int jc = j < N ? j : N - 1;
-		const int patch = jc / PI, q = jc - patch * PI, qy = q / SI, qx = q - qy * SI;
-		bool ok[9];
-#pragma unroll
-		for (int t = 0; t < 9; ++t) {
-			const int y = qy - t / 3, x = qx - t % 3;
-			ok[t] = y >= 0 && y < SO && x >= 0 && x < SO;
-		}
-		// g[patch][co = 4s + kg][qy - ky][qx - kx]; out-of-range taps read 0 (the offsets are only formed where valid)
-		const int gb = patch * FM * PO + kg * PO + qy * SO + qx;
-		const float *pa = w + kg * FM * 9 + i * 9;
-		for (int s = 0; s < FM / 4; ++s, pa += 4 * FM * 9) {
-			float a[9];
-#pragma unroll
-			for (int t = 0; t < 9; ++t) a[t] = pa[t];
-			const int base = gb + s * 4 * PO;
-#pragma unroll
-			for (int t = 0; t < 9; ++t) acc = mfma(a[t], ok[t] ? g[base - (t / 3) * SO - t % 3] : 0.f, acc);
-		}
-	};
-	auto put = [&](int ci, int j, float v) {
-		const int patch = j / PI, q = j - patch * PI;
-		float *p = in + (patch * FM + ci) * PI + q;
-		*p = *p > 0.f ? v : 0.f;
-	};
-	block_gemm(N, mac, put);
-}
-
 // the four convolutions of a pair's patches X into A1 .. A4, all in LDS
 __device__ __forceinline__ void tower_forward(const float *__restrict__ params, float *lds)
 {
 	float *X = lds + L_X, *A1 = lds + L_A1, *A2 = lds + L_A2, *A3 = lds + L_A3, *A4 = lds + L_A4;
-	conv_forward<1, S0>(params + off_w(1), params + off_b(1), X, A1);
+	conv_forward<NP, 1, S0>(params + off_w(1), params + off_b(1), X, A1);
 	__syncthreads();
-	conv_forward<FM, S1>(params + off_w(2), params + off_b(2), A1, A2);
+	conv_forward<NP, FM, S1>(params + off_w(2), params + off_b(2), A1, A2);
 	__syncthreads();
-	conv_forward<FM, S2>(params + off_w(3), params + off_b(3), A2, A3);
+	conv_forward<NP, FM, S2>(params + off_w(3), params + off_b(3), A2, A3);
 	__syncthreads();
-	conv_forward<FM, S3>(params + off_w(4), params + off_b(4), A3, A4);
+	conv_forward<NP, FM, S3>(params + off_w(4), params + off_b(4), A3, A4);
 	__syncthreads();
 }
 
@@ -252,158 +134,19 @@ __global__ void __launch_bounds__(NT) tower_backward_kernel(const float *__restr
 	}
 	__syncthreads();
 	float *g = slab + (int64_t)pair * NCONV;
-	conv_weight_grad<FM, S3>(A4, A3, g + off_w(4), g + off_b(4));
+	conv_weight_grad<NP, FM, S3>(A4, A3, g + off_w(4), g + off_b(4));
 	__syncthreads();
-	conv_data_grad<S3>(params + off_w(4), A4, A3);
+	conv_data_grad<NP, S3>(params + off_w(4), A4, A3);
 	__syncthreads();
-	conv_weight_grad<FM, S2>(A3, A2, g + off_w(3), g + off_b(3));
+	conv_weight_grad<NP, FM, S2>(A3, A2, g + off_w(3), g + off_b(3));
 	__syncthreads();
-	conv_data_grad<S2>(params + off_w(3), A3, A2);
+	conv_data_grad<NP, S2>(params + off_w(3), A3, A2);
 	__syncthreads();
-	conv_weight_grad<FM, S1>(A2, A1, g + off_w(2), g + off_b(2));
+	conv_weight_grad<NP, FM, S1>(A2, A1, g + off_w(2), g + off_b(2));
 	__syncthreads();
-	conv_data_grad<S1>(params + off_w(2), A2, A1);
+	conv_data_grad<NP, S1>(params + off_w(2), A2, A1);
 	__syncthreads();
-	conv_weight_grad<1, S0>(A1, X, g + off_w(1), g + off_b(1));
-}
-
-// ---- the FC stack: batch GEMMs over the R = 2 * n_pairs rows, one wave per 16 x 16 tile ---------------------------------
-constexpr int FC_WAVES = 4;   // tiles per workgroup
-
-// Launches 2-5: out (R, 384) = ReLU(in (R, K) w (384, K)^T + b).  Both operands are contiguous along K: a lane loads four
-// consecutive k as one float4, so K step 4c + j of the instruction sequence is k = 16c + 4 * (lane>>4) + j.
-__global__ void __launch_bounds__(FC_WAVES * 64) fc_forward_kernel(const float *__restrict__ in, int K, const float *__restrict__ w,
-                                                                   const float *__restrict__ b, float *__restrict__ out, int R)
-{
-	const int lane = threadIdx.x & 63, kg = lane >> 4, l = lane & 15;
-	const int task = blockIdx.x * FC_WAVES + (threadIdx.x >> 6);
-	const int ntn = NH / 16;
-	if (task >= (R + 15) / 16 * ntn) return;
-	const int mt = task / ntn, nt = task - mt * ntn;
-	const int row = mt * 16 + l, col = nt * 16 + l;
-	const float *pa = in + (int64_t)(row < R ? row : R - 1) * K + 4 * kg;
-	const float *pb = w + (int64_t)col * K + 4 * kg;
-	floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-	for (int c = 0; c < K; c += 16) {
-		const float4 a = *(const float4 *)(pa + c), v = *(const float4 *)(pb + c);
-		acc = mfma(a.x, v.x, acc);
-		acc = mfma(a.y, v.y, acc);
-		acc = mfma(a.z, v.z, acc);
-		acc = mfma(a.w, v.w, acc);
-	}
-	const float bias = b[col];
-	for (int r = 0; r < 4; ++r) {
-		const int orow = mt * 16 + 4 * kg + r;
-		if (orow < R) out[(int64_t)orow * NH + col] = fmaxf(acc[r] + bias, 0.f);
-	}
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-	return v;
-}
-
-// Launch 6, one workgroup: z = a4 w5 + b5, o = Sigmoid(z), BCECriterion2 with target r & 1 and its gradient in the
-// reference's operation order (BCECriterion2.lua), Sigmoid's backward, then dw5, db5, the loss and g4 = (g5 w5) masked by a4.
-constexpr int HEAD_NT = 1024;
-__global__ void __launch_bounds__(HEAD_NT) fc_head_kernel(const float *__restrict__ a4, const float *__restrict__ w5, const float *__restrict__ b5,
-                                                          int R, float *__restrict__ g4, float *__restrict__ dw5, float *__restrict__ db5,
-                                                          float *__restrict__ loss_out)
-{
-	__shared__ float g5[2 * MC_TRAIN_SLOW_MAX_PAIRS], term[2 * MC_TRAIN_SLOW_MAX_PAIRS];
-	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-	const float eps = 1e-12f, n = (float)R;
-	for (int r = wave; r < R; r += HEAD_NT / 64) {
-		float z = 0.f;
-		for (int c = lane; c < NH; c += 64) z += a4[(int64_t)r * NH + c] * w5[c];
-		z = wave_sum(z) + b5[0];
-		const float o = 1.f / (1.f + expf(-z));
-		const float tg = (float)(r & 1);
-		const float t1 = 1.f - tg;
-		const float t2 = (1.f - o) + eps;
-		const float t3 = o + eps;
-		if (lane == 0) {
-			term[r] = (logf(t3) * tg + logf(t2) * t1) / n;
-			const float go = -((tg / t3 - t1 / t2) / n);
-			g5[r] = go * ((1.f - o) * o);
-		}
-	}
-	__syncthreads();
-	if (t < NH) {
-		float s = 0.f;
-		for (int r = 0; r < R; ++r) s += g5[r] * a4[(int64_t)r * NH + t];
-		dw5[t] = s;
-	} else if (t == NH) {
-		float s = 0.f;
-		for (int r = 0; r < R; ++r) s += g5[r];
-		db5[0] = s;
-	} else if (t == NH + 64) {
-		float s = 0.f;
-		for (int r = 0; r < R; ++r) s += term[r];
-		loss_out[0] = -s;
-	}
-	for (int e = t; e < R * NH; e += HEAD_NT) {
-		const int r = e / NH, c = e - r * NH;
-		g4[e] = a4[e] > 0.f ? g5[r] * w5[c] : 0.f;
-	}
-}
-
-// Launches 7-10, for the Linear w (384, K) with input ap (R, K) and output gradient g (R, 384).  A wave's task is one of
-//   data    gp[r, k]  = sum_c g[r, c] w[c, k], masked by ap[r, k] > 0 where MASK   (R x K, summed over c in order)
-//   weight  dw[c, k]  = sum_r g[r, c] ap[r, k]                                      (384 x K, summed over the rows in order)
-//   bias    db[c]     = sum_r g[r, c]                                               (64 columns per wave)
-template <bool MASK>
-__global__ void __launch_bounds__(FC_WAVES * 64) fc_backward_kernel(const float *__restrict__ g, const float *__restrict__ ap, int K,
-                                                                    const float *__restrict__ w, int R, float *__restrict__ gp,
-                                                                    float *__restrict__ dw, float *__restrict__ db)
-{
-	const int lane = threadIdx.x & 63, kg = lane >> 4, l = lane & 15;
-	int task = blockIdx.x * FC_WAVES + (threadIdx.x >> 6);
-	const int nkt = K / 16, n_data = (R + 15) / 16 * nkt, n_weight = NH / 16 * nkt, n_bias = NH / 64;
-	if (task < n_data) {
-		const int mt = task / nkt, nt = task - mt * nkt;
-		const int row = mt * 16 + l, col = nt * 16 + l;
-		const float *pa = g + (int64_t)(row < R ? row : R - 1) * NH + 4 * kg;
-		const float *pb = w + (int64_t)(4 * kg) * K + col;
-		floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-		for (int c = 0; c < NH; c += 16, pb += 16 * K) {
-			const float4 a = *(const float4 *)(pa + c);
-			acc = mfma(a.x, pb[0], acc);
-			acc = mfma(a.y, pb[K], acc);
-			acc = mfma(a.z, pb[2 * K], acc);
-			acc = mfma(a.w, pb[3 * K], acc);
-		}
-		for (int r = 0; r < 4; ++r) {
-			const int orow = mt * 16 + 4 * kg + r;
-			if (orow < R) {
-				const int64_t e = (int64_t)orow * K + col;
-				gp[e] = !MASK || ap[e] > 0.f ? acc[r] : 0.f;
-			}
-		}
-		return;
-	}
-	task -= n_data;
-	if (task < n_weight) {
-		const int mt = task / nkt, nt = task - mt * nkt;
-		const int m = mt * 16 + l, col = nt * 16 + l;
-		floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-		for (int r0 = 0; r0 < R; r0 += 4) {
-			const int r = r0 + kg;
-			const float a = r < R ? g[(int64_t)r * NH + m] : 0.f;
-			const float v = r < R ? ap[(int64_t)r * K + col] : 0.f;
-			acc = mfma(a, v, acc);
-		}
-		for (int r = 0; r < 4; ++r) dw[(int64_t)(mt * 16 + 4 * kg + r) * K + col] = acc[r];
-		return;
-	}
-	task -= n_weight;
-	if (task < n_bias) {
-		const int c = task * 64 + lane;
-		float s = 0.f;
-		for (int r = 0; r < R; ++r) s += g[(int64_t)r * NH + c];
-		db[c] = s;
-	}
+	conv_weight_grad<NP, 1, S0>(A1, X, g + off_w(1), g + off_b(1));
 }
 
 // Launch 12: the convolutions' gradient is the slab's rows summed in pair order, the FC stack's is gfc as it is;
@@ -413,16 +156,7 @@ __global__ void __launch_bounds__(256) sgd_kernel(const float *__restrict__ slab
 {
 	const int j = blockIdx.x * blockDim.x + threadIdx.x;
 	if (j >= NPARAMS) return;
-	float g;
-	if (j < NCONV) {
-		g = 0.f;
-		for (int p = 0; p < n_pairs; ++p) g += slab[(int64_t)p * NCONV + j];
-	} else {
-		g = gfc[j - NCONV];
-	}
-	const float v = moms[j] * mom - lr * g;
-	moms[j] = v;
-	params[j] = params[j] + v;
+	sgd_update(j, slab, gfc, n_pairs, NCONV, params, moms, lr, mom);
 }
 
 // ---- the workspace ---------------------------------------------------------------------------------------------------

@@ -24,8 +24,10 @@ net/net_<args>.t7; train_tr then runs test_te.  `-a test_te | test_all`
 the mean error.  Training flags keep main.lua's names and defaults; -epochs and -max_steps shorten a run.  `-at 1` trains
 and tests on data.kitti and data.kitti2015 together (main.lua:403-426).  `python -m mc_cnn_amd.preprocess_kitti` writes
 both sets from the KITTI archives (preprocess_kitti.lua).  `mb fast -a train_tr | train_all | test_te` train and test
-Middlebury's five-layer fast net (train_mb.py, libmctrainmb.so, with train_mb.parse's flags) from preprocess_mb.py's
-`data.mb.<rect>_<color>`; mb slow training, -a test_all on mb and -a submit are out of scope.
+Middlebury's five-layer fast net (train_mb.py, libmctrainmb.so, with train_mb.parse's flags) and
+`mb slow -a train_tr | train_all | test_te` its accurate net (train_mb_slow.py, libmctrainmbslow.so, with
+train_mb_slow.parse's flags) from preprocess_mb.py's `data.mb.<rect>_<color>`; -a test_all on mb and -a submit are out of
+scope.
 """
 import argparse
 import sys
@@ -85,8 +87,9 @@ def parse(argv):
     if opt.a not in ("predict", "time") and (opt.a not in TRAIN_ACTIONS or dataset not in ("kitti", "kitti2015") or arch != "fast"):
         raise SystemExit("main.py: -a %s is not supported for %s %s; training and testing cover -a %s for "
                          "{kitti|kitti2015} fast only (arch slow trains through train_slow.parse, which main() routes "
-                         "{kitti|kitti2015} slow to, mb fast -a train_tr | train_all | test_te through train_mb.parse; mb slow "
-                         "training, -a test_all on mb and -a submit are out of scope)"
+                         "{kitti|kitti2015} slow to, mb fast -a train_tr | train_all | test_te through train_mb.parse, mb slow "
+                         "-a train_tr | train_all | test_te through train_mb_slow.parse; -a test_all on mb and -a submit are "
+                         "out of scope)"
                          % (opt.a, dataset, arch, " | ".join(TRAIN_ACTIONS)))
     if getattr(opt, "at", 0) == 1 and opt.data_dir:
         raise SystemExit("main.py: -at 1 reads data.kitti and data.kitti2015 together (main.lua:403-426) and takes no -data_dir")
@@ -244,6 +247,13 @@ def trains_mb(argv):
             and argv[argv.index("-a", 2) + 1] in ACTIONS)
 
 
+def trains_mb_slow(argv):
+    """mb slow -a train_tr|train_all|test_te: train_mb_slow.parse's command lines (parse refuses them)."""
+    from .train_mb import ACTIONS
+    return (len(argv) >= 2 and argv[0] == "mb" and argv[1] == "slow" and "-a" in argv[2:-1]
+            and argv[argv.index("-a", 2) + 1] in ACTIONS)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if trains_slow(argv):
@@ -252,6 +262,9 @@ def main(argv=None):
     elif trains_mb(argv):
         from . import train_mb
         dataset, arch, opt, prm = train_mb.parse(argv)
+    elif trains_mb_slow(argv):
+        from . import train_mb, train_mb_slow
+        dataset, arch, opt, prm = train_mb_slow.parse(argv)
     else:
         dataset, arch, opt, prm = parse(argv)
     import torch
@@ -282,13 +295,15 @@ def main(argv=None):
                                         want_volumes=want_volumes)
         raw = raw_volumes_slow(features_slow(x_batch, layers), fc_layers, D, prm["border_n"])
         return stereo_predict_fused(x_batch, prm, D, raw=raw, workspace=workspace, want_volumes=want_volumes)
-    if dataset == "mb" and opt.a in TRAIN_ACTIONS:   # train_mb.parse's: train_tr | train_all | test_te
+    if dataset == "mb" and opt.a in TRAIN_ACTIONS:   # train_mb.parse's and train_mb_slow.parse's: train_tr | train_all | test_te
         if opt.a != "test_te":
-            opt.net_fname = train_mb.train(opt, argv[2:], dev)
+            opt.net_fname = train_mb_slow.train(opt, argv[2:], dev) if arch == "slow" else train_mb.train(opt, argv[2:], dev)
             if opt.a == "train_all":
                 return 0
             opt.a = "test_te"
             layers[:] = device_layers(load_net(opt.net_fname, dataset, arch), dev)
+            if arch == "slow":
+                fc_layers[:] = load_fc(opt.net_fname, dataset)
         train_mb.evaluate(opt, prm, run, dev)          # main.lua:1124-1130, 1183-1238
         return 0
     if opt.a in TRAIN_ACTIONS:

@@ -20,7 +20,7 @@ length of its set's dispnoc.bin.  The sets come from `python -m mc_cnn_amd.prepr
 
 Arch slow trains through train_slow.py (libmctrainslow.so), which reuses this module's data, draws and evaluation;
 `mb fast` through train_mb.py (libmctrainmb.so), which reuses the draws, the epoch schedule, the saved net and the error.
-Not covered: mb slow, -subset, -debug, -a submit, multi-GPU.
+Not covered (mb slow trains through train_mb_slow.py): -subset, -debug, -a submit, multi-GPU.
 """
 import math
 import os

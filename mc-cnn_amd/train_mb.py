@@ -18,7 +18,8 @@ What is Middlebury's own:
 
 The draws are the reference's distributions from one numpy Generator(-seed), not Torch's Mersenne-Twister stream (see
 train.py).  `preprocess_mb.py` is not part of this project: `-data_dir` (default data.mb.<rect>_<color>) has to hold its
-output.  Not covered: -color rgb, mb slow, -a submit, -a test_all (main.lua:1136 asserts it away itself), -subset, -debug.
+output.  `mb slow` trains through train_mb_slow.py.  Not covered: -color rgb, -a submit, -a test_all (main.lua:1136 asserts it
+away itself), -subset, -debug.
 """
 import argparse
 import os
@@ -45,7 +46,8 @@ def parse(argv):
     from .params import SM_SKIP, SM_TERMINATE, TABLES
     if len(argv) >= 2 and argv[0] == "mb" and argv[1] == "slow":
         raise SystemExit("train_mb: mb slow is not trained here: its net (l1 5, fm 112, l2 3) keeps 221 KB of activations per "
-                         "pair, more than the one-workgroup-per-pair step of libmctrainmb.so can hold in a CU's LDS")
+                         "pair, more than the one-workgroup-per-pair step of libmctrainmb.so can hold in a CU's LDS; "
+                         "train_mb_slow.parse takes these command lines (libmctrainmbslow.so, one workgroup per patch)")
     if len(argv) < 2 or argv[0] != "mb" or argv[1] != "fast":
         raise SystemExit("train_mb: training and testing on Middlebury cover mb fast -a %s" % " | ".join(ACTIONS))
     t = TABLES[("mb", "fast")]

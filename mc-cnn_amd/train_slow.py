@@ -10,7 +10,8 @@ The initial weights (`init_net`) have the ranges of nn.SpatialConvolution:reset 
 small synthetic sets the net sits on a plateau from there (its output is a constant, the loss stays at ln 2 for thousands
 of steps: README.md); `train(..., init=(conv_layers, fc_layers))` starts from given nets instead.
 
-Not covered: Middlebury's accurate net (l1 5, l2 3; `mb fast` trains through train_mb.py), -subset, -debug, -a submit.
+Middlebury's accurate net (l1 5, l2 3) trains through train_mb_slow.py, `mb fast` through train_mb.py.  Not covered:
+-subset, -debug, -a submit.
 """
 import argparse
 import os
@@ -179,7 +180,7 @@ def parse(argv):
     from .params import SM_SKIP, SM_TERMINATE, TABLES
     if len(argv) < 2 or argv[0] not in ("kitti", "kitti2015") or argv[1] != "slow":
         raise SystemExit("train_slow: training and testing of arch slow cover {kitti|kitti2015} slow -a %s "
-                         "(mb slow's l1 5 / l2 3 net and -a submit are out of scope; mb fast trains through train_mb.parse)" % " | ".join(ACTIONS))
+                         "(mb slow's l1 5 / l2 3 net trains through train_mb_slow.parse, mb fast through train_mb.parse; -a submit is out of scope)" % " | ".join(ACTIONS))
     dataset = argv[0]
     t = TABLES[(dataset, "slow")]
     ap = argparse.ArgumentParser(prog="main.py %s slow" % dataset, prefix_chars="-")

@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVENTORY = os.path.join(ROOT, "tests", "kernel_inventory.txt")
 INVENTORY_TRAIN_SLOW = os.path.join(ROOT, "tests", "kernel_inventory_train_slow.txt")   # libmctrainslow.so
 INVENTORY_TRAIN_MB = os.path.join(ROOT, "tests", "kernel_inventory_train_mb.txt")       # libmctrainmb.so
+INVENTORY_TRAIN_MB_SLOW = os.path.join(ROOT, "tests", "kernel_inventory_train_mb_slow.txt")   # libmctrainmbslow.so (shares the FC kernels' names with libmctrainslow.so)
 NAMESPACE = "mc::"
 
 
@@ -83,7 +84,7 @@ def launched(csv_paths):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("stats", nargs="+", help="kernel_stats.csv of rocprofv3 --kernel-trace --stats")
-    ap.add_argument("--inventory", nargs="+", default=[INVENTORY, INVENTORY_TRAIN_SLOW, INVENTORY_TRAIN_MB])
+    ap.add_argument("--inventory", nargs="+", default=[INVENTORY, INVENTORY_TRAIN_SLOW, INVENTORY_TRAIN_MB, INVENTORY_TRAIN_MB_SLOW])
     a = ap.parse_args(argv)
     inv = {}
     for path in a.inventory:

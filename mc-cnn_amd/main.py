@@ -19,7 +19,8 @@ w1,b1,...,w<l1>,b<l1> (w_i: (fm, in, 3, 3); arch slow also fw1,fb1,...), or `ran
 
 `-a train_tr | train_all` (kitti | kitti2015; main.lua:602-890) train the net on the GPU from `-data_dir` (arch fast:
 train.py, libmctrain.so; arch slow: train_slow.py, libmctrainslow.so, with train_slow.parse's flags) and save
-net/net_<args>.t7; train_tr then runs test_te.  `-a test_te | test_all`
+net/net_<args>.t7; train_tr then runs test_te.  `training_module` is the one routing table of the four trainable nets, whose
+shared host side is train_common.py.  `-a test_te | test_all`
 (main.lua:1121-1138, 1172-1293) predict the dataset's test (all) pairs with -net_fname and print `runtime err` per pair and
 the mean error.  Training flags keep main.lua's names and defaults; -epochs and -max_steps shorten a run.  `-at 1` trains
 and tests on data.kitti and data.kitti2015 together (main.lua:403-426).  `python -m mc_cnn_amd.preprocess_kitti` writes
@@ -29,14 +30,14 @@ Middlebury's five-layer fast net (train_mb.py, libmctrainmb.so, with train_mb.pa
 train_mb_slow.parse's flags) from preprocess_mb.py's `data.mb.<rect>_<color>`; -a test_all on mb and -a submit are out of
 scope.
 """
-import argparse
 import sys
 import time
 
 import numpy as np
 
 from .binio import write_bin
-from .params import NET_SHAPES, SM_SKIP, SM_TERMINATE, TABLES
+from .params import NET_SHAPES, TABLES
+from .train_common import new_parser, pipeline_prm
 
 
 def rgb2y(img):
@@ -68,21 +69,16 @@ def parse(argv):
                          "test_all} [flags]  (main.lua:10-13)")
     dataset, arch = argv[0], argv[1]
     t = TABLES[(dataset, arch)]
-    ap = argparse.ArgumentParser(prog="main.py %s %s" % (dataset, arch), prefix_chars="-")
+    ap = new_parser(dataset, arch, t, FAST_TRAIN_DEFAULTS)
     ap.add_argument("-a", default="predict", choices=["predict", "time"] + list(TRAIN_ACTIONS) + ["submit"])
-    ap.add_argument("-net_fname", default="random:42")
     ap.add_argument("-left", default="")
     ap.add_argument("-right", default="")
     ap.add_argument("-disp_max", type=int, default=228 if dataset != "mb" else 200)
-    ap.add_argument("-gpu", type=int, default=1, help="1-based, as cutorch.setDevice (main.lua:16,342)")
     ap.add_argument("-tiny", action="store_true")
-    for k in ("L1", "cbca_i1", "cbca_i2", "sgm_i"):
-        ap.add_argument("-" + k, type=int, default=t[k])
-    for k in ("tau1", "pi1", "pi2", "sgm_q1", "sgm_q2", "alpha1", "tau_so", "blur_sigma", "blur_t"):
-        ap.add_argument("-" + k, type=float, default=t[k])
-    ap.add_argument("-sm_terminate", default="", choices=sorted(SM_TERMINATE), help="main.lua:25")
-    ap.add_argument("-sm_skip", default="", choices=sorted(SM_SKIP), help="main.lua:26")
-    add_train_flags(ap, dataset)
+    ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
+    if dataset in ("kitti", "kitti2015"):
+        ap.add_argument("-at", type=int, default=0, choices=(0, 1),
+                        help="1: train on KITTI 2012 and 2015 together (main.lua:72,208,236, 403-426)")
     opt = ap.parse_args(argv[2:])
     if opt.a not in ("predict", "time") and (opt.a not in TRAIN_ACTIONS or dataset not in ("kitti", "kitti2015") or arch != "fast"):
         raise SystemExit("main.py: -a %s is not supported for %s %s; training and testing cover -a %s for "
@@ -93,41 +89,12 @@ def parse(argv):
                          % (opt.a, dataset, arch, " | ".join(TRAIN_ACTIONS)))
     if getattr(opt, "at", 0) == 1 and opt.data_dir:
         raise SystemExit("main.py: -at 1 reads data.kitti and data.kitti2015 together (main.lua:403-426) and takes no -data_dir")
-    prm = dict(t)
-    prm["sm_terminate"], prm["sm_skip"] = opt.sm_terminate, opt.sm_skip   # make_params maps the stage names
-    for k in ("L1", "cbca_i1", "cbca_i2", "sgm_i", "tau1", "pi1", "pi2", "sgm_q1", "sgm_q2", "alpha1", "tau_so", "blur_sigma",
-              "blur_t"):
-        prm[k] = getattr(opt, k)
-    return dataset, arch, opt, prm
+    return dataset, arch, opt, pipeline_prm(t, opt)
 
 
 TRAIN_ACTIONS = ("train_tr", "train_all", "test_te", "test_all")
 
-# main.lua:33-64 (augmentation, per dataset) and 207-220, 236-248 (arch fast training); the mb values are train_mb.parse's
-AUG_DEFAULTS = {
-    "kitti": dict(hflip=0, vflip=0, rotate=7, hscale=0.9, scale=1, trans=0, hshear=0.1, brightness=0.7, contrast=1.3,
-                  d_vtrans=0, d_rotate=0, d_hscale=1, d_hshear=0, d_brightness=0.3, d_contrast=1),
-    "mb": dict(hflip=0, vflip=0, rotate=28, hscale=0.8, scale=0.8, trans=0, hshear=0.1, brightness=1.3, contrast=1.1,
-               d_vtrans=1, d_rotate=3, d_hscale=0.9, d_hshear=0.3, d_brightness=0.7, d_contrast=1.1),
-}
-AUG_DEFAULTS["kitti2015"] = AUG_DEFAULTS["kitti"]
-FAST_TRAIN_DEFAULTS = dict(m=0.2, pow=1, lr=0.002, bs=128, mom=0.9, true1=1, false1=4, false2=10)
-
-
-def add_train_flags(ap, dataset):
-    """The flags of main.lua's training path with its names and defaults (arch fast's values for the optimiser)."""
-    ap.add_argument("-seed", type=int, default=42)
-    for k, v in FAST_TRAIN_DEFAULTS.items():
-        ap.add_argument("-" + k, type=type(v), default=v)
-    for k, v in AUG_DEFAULTS[dataset].items():
-        ap.add_argument("-" + k, type=int if k in ("hflip", "vflip") else float, default=float(v) if k not in ("hflip", "vflip") else v)
-    ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
-    if dataset in ("kitti", "kitti2015"):
-        ap.add_argument("-at", type=int, default=0, choices=(0, 1),
-                        help="1: train on KITTI 2012 and 2015 together (main.lua:72,208,236, 403-426)")
-    ap.add_argument("-epochs", type=int, default=14, help="main.lua:777 runs 14")
-    ap.add_argument("-max_steps", type=int, default=0, help="stop training after this many steps in all (0: no limit)")
-
+FAST_TRAIN_DEFAULTS = dict(m=0.2, pow=1, lr=0.002, bs=128, mom=0.9, true1=1, false1=4, false2=10)   # main.lua:207-220, 236-248
 
 FC_SHAPES = {"kitti": (4, 384), "kitti2015": (4, 384), "mb": (3, 384)}  # (l2, nh2), main.lua:76-77, 123-124
 
@@ -234,39 +201,22 @@ def features_fast(x_batch, layers):
     return out
 
 
-def trains_slow(argv):
-    """{kitti|kitti2015} slow -a train_tr|train_all|test_te|test_all: train_slow.parse's command lines (parse refuses them)."""
-    return (len(argv) >= 2 and argv[0] in ("kitti", "kitti2015") and argv[1] == "slow" and "-a" in argv[2:-1]
-            and argv[argv.index("-a", 2) + 1] in TRAIN_ACTIONS)
-
-
-def trains_mb(argv):
-    """mb fast -a train_tr|train_all|test_te: train_mb.parse's command lines (parse refuses them)."""
-    from .train_mb import ACTIONS
-    return (len(argv) >= 2 and argv[0] == "mb" and argv[1] == "fast" and "-a" in argv[2:-1]
-            and argv[argv.index("-a", 2) + 1] in ACTIONS)
-
-
-def trains_mb_slow(argv):
-    """mb slow -a train_tr|train_all|test_te: train_mb_slow.parse's command lines (parse refuses them)."""
-    from .train_mb import ACTIONS
-    return (len(argv) >= 2 and argv[0] == "mb" and argv[1] == "slow" and "-a" in argv[2:-1]
-            and argv[argv.index("-a", 2) + 1] in ACTIONS)
+def training_module(argv):
+    """The module whose `parse` takes argv, with its `train` and `evaluate`: train_slow for {kitti|kitti2015} slow, train_mb for
+    mb fast and train_mb_slow for mb slow, each with `-a` one of its ACTIONS.  None for every other command line: `parse`
+    above takes or refuses those ({kitti|kitti2015} fast trains through train.py)."""
+    if len(argv) < 2 or "-a" not in argv[2:-1]:
+        return None
+    from . import train_mb, train_mb_slow, train_slow
+    routes = {("kitti", "slow"): train_slow, ("kitti2015", "slow"): train_slow, ("mb", "fast"): train_mb, ("mb", "slow"): train_mb_slow}
+    mod = routes.get((argv[0], argv[1]))
+    return mod if mod is not None and argv[argv.index("-a", 2) + 1] in mod.ACTIONS else None
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if trains_slow(argv):
-        from . import train_slow
-        dataset, arch, opt, prm = train_slow.parse(argv)
-    elif trains_mb(argv):
-        from . import train_mb
-        dataset, arch, opt, prm = train_mb.parse(argv)
-    elif trains_mb_slow(argv):
-        from . import train_mb, train_mb_slow
-        dataset, arch, opt, prm = train_mb_slow.parse(argv)
-    else:
-        dataset, arch, opt, prm = parse(argv)
+    mod = training_module(argv)
+    dataset, arch, opt, prm = parse(argv) if mod is None else mod.parse(argv)
     import torch
     from .predict import Workspace, stereo_predict_fused
     if arch not in ("fast", "slow", "ad", "census"):
@@ -295,31 +245,22 @@ def main(argv=None):
                                         want_volumes=want_volumes)
         raw = raw_volumes_slow(features_slow(x_batch, layers), fc_layers, D, prm["border_n"])
         return stereo_predict_fused(x_batch, prm, D, raw=raw, workspace=workspace, want_volumes=want_volumes)
-    if dataset == "mb" and opt.a in TRAIN_ACTIONS:   # train_mb.parse's and train_mb_slow.parse's: train_tr | train_all | test_te
-        if opt.a != "test_te":
-            opt.net_fname = train_mb_slow.train(opt, argv[2:], dev) if arch == "slow" else train_mb.train(opt, argv[2:], dev)
-            if opt.a == "train_all":
-                return 0
-            opt.a = "test_te"
-            layers[:] = device_layers(load_net(opt.net_fname, dataset, arch), dev)
-            if arch == "slow":
-                fc_layers[:] = load_fc(opt.net_fname, dataset)
-        train_mb.evaluate(opt, prm, run, dev)          # main.lua:1124-1130, 1183-1238
-        return 0
     if opt.a in TRAIN_ACTIONS:
-        from . import train
-        if opt.a in ("train_tr", "train_all"):   # main.lua:602-890
-            if arch == "slow":
-                opt.net_fname = train_slow.train(dataset, opt, argv[2:], dev)
-            else:
-                opt.net_fname = train.train(dataset, arch, opt, argv[2:], dev)
+        if mod is None:
+            from . import train as mod
+        if opt.a in ("train_tr", "train_all"):   # main.lua:602-890; each train() keeps its own leading arguments
+            lead = () if dataset == "mb" else (dataset, arch) if arch == "fast" else (dataset,)
+            opt.net_fname = mod.train(*lead, opt, argv[2:], dev)
             if opt.a == "train_all":            # main.lua:884-887 goes on to submit, which is out of scope
                 return 0
             opt.a = "test_te"
             layers[:] = device_layers(load_net(opt.net_fname, dataset, arch), dev)
             if arch == "slow":
                 fc_layers[:] = load_fc(opt.net_fname, dataset)
-        train.evaluate(dataset, opt, run, dev)   # main.lua:1121-1138, 1172-1293
+        if dataset == "mb":
+            mod.evaluate(opt, prm, run, dev)         # main.lua:1124-1130, 1183-1238
+        else:
+            mod.evaluate(dataset, opt, run, dev)     # main.lua:1121-1138, 1172-1293
         return 0
     if opt.a == "time":  # main.lua:1140-1167
         if dataset == "mb":

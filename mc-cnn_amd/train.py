@@ -18,18 +18,22 @@ images, then the chosen set's test images (for kitti2015 from 2015 image n_tr on
 indices and nnz image ids are shifted by 2012's n_tr.  main.lua hard-codes the two n_tr (194, 200); here each is the
 length of its set's dispnoc.bin.  The sets come from `python -m mc_cnn_amd.preprocess_kitti`.
 
-Arch slow trains through train_slow.py (libmctrainslow.so), which reuses this module's data, draws and evaluation;
-`mb fast` through train_mb.py (libmctrainmb.so), which reuses the draws, the epoch schedule, the saved net and the error.
-Not covered (mb slow trains through train_mb_slow.py): -subset, -debug, -a submit, multi-GPU.
+What the four trainable nets have in common is train_common.py's: the draws and the epoch loop (`draw_params`,
+`run_epochs`), the flat parameter layout (`NetShape`), the Trainer's common device state (`TrainerBase`) and `step_batch`.
+This module adds the KITTI data, the image store (`KittiTrainer`), libmctrain.so's `run` and `sample`, the saved fast net
+and the evaluation; train_slow.py (libmctrainslow.so) reuses the data, the store and the evaluation, train_mb.py
+(libmctrainmb.so) and train_mb_slow.py the saved net and the error.
+Not covered: -subset, -debug, -a submit, multi-GPU.
 """
-import math
 import os
 import time
 
 import numpy as np
 
 from . import _train_lib as tl
+from . import train_common as common
 from .binio import dims, fromfile
+from .train_common import NetShape, TrainerBase, _p, _stream, draw_params, n_steps_per_epoch, run_epochs, training_rows  # noqa: F401
 
 CHUNK_STEPS = 256           # steps enqueued per mc_train_run call (one chunk of parameter draws)
 DATA_FILES = ("x0", "x1", "metadata", "tr", "te", "nnz_tr", "nnz_te")
@@ -74,104 +78,37 @@ def load_data_at(dataset, names=DATA_FILES, dirs=AT_DIRS):
     return out
 
 
-def flat_params(layers):
-    """[(w, b)] of the fast net -> one float32 vector in include/mc_train.h's order (w1 b1 w2 b2 w3 b3 w4 b4)."""
-    out = np.concatenate([np.concatenate([np.asarray(w, np.float32).ravel(), np.asarray(b, np.float32).ravel()]) for w, b in layers])
-    if out.size != tl.NPARAMS:
-        raise ValueError("fast net of %d parameters, libmctrain.so trains %d (l1 4, fm 64, 1 input plane)" % (out.size, tl.NPARAMS))
-    return out
+NET = NetShape(tl.L1, tl.FM, 0, 0, tl.NPARAMS, "libmctrain.so")
+flat_params = NET.flat_params     # [(w, b)] of the fast net -> one float32 vector in include/mc_train.h's order (w1 b1 .. w4 b4)
 
 
 def unflat_params(v):
-    v = np.asarray(v, np.float32)
-    layers, o = [], 0
-    for i in range(tl.L1):
-        cin = 1 if i == 0 else tl.FM
-        n = tl.FM * cin * 9
-        layers.append((v[o:o + n].reshape(tl.FM, cin, 3, 3).copy(), v[o + n:o + n + tl.FM].copy()))
-        o += n + tl.FM
-    return layers
+    return NET.unflat_params(v)[0]
 
 
-def n_steps_per_epoch(n, bs):
-    """`for t = 1, n - bs/2, bs/2` (main.lua:787)."""
-    return len(range(1, n - bs // 2 + 1, bs // 2))
+class KittiTrainer(TrainerBase):
+    """TrainerBase and the image store of a KITTI set: x0, x1 as (n_img, H, W) on the device."""
 
-
-def draw_params(rng, opt, n_steps, n_pairs):
-    """The augmentation parameters of main.lua:790-814 for n_steps x n_pairs pairs, (n_steps, n_pairs, 18) float32 in the
-    order of include/mc_train.h.  Vectorised numpy draws: the distributions and flags of the reference, not its stream."""
-    sh = (n_steps, n_pairs)
-    u = lambda a, b: rng.uniform(a, b, sh)
-    assert opt.hscale <= 1 and opt.scale <= 1
-    assert opt.contrast >= 1 and opt.d_contrast >= 1
-    d_pos = u(-opt.true1, opt.true1)
-    d_neg = u(opt.false1, opt.false2)
-    d_neg = np.where(rng.uniform(0, 1, sh) < 0.5, -d_neg, d_neg)
-    s = u(opt.scale, 1)
-    sx, sy = s * u(opt.hscale, 1), s
-    if opt.hflip == 1:
-        sx = np.where(rng.uniform(0, 1, sh) < 0.5, -sx, sx)
-    if opt.vflip == 1:
-        sy = np.where(rng.uniform(0, 1, sh) < 0.5, -sy, sy)
-    hshear = u(-opt.hshear, opt.hshear)
-    tx, ty = u(-opt.trans, opt.trans), u(-opt.trans, opt.trans)
-    rot = opt.rotate * math.pi / 180
-    phi = u(-rot, rot)
-    brightness = u(-opt.brightness, opt.brightness)
-    contrast = u(1 / opt.contrast, opt.contrast)
-    sx_ = sx * u(opt.d_hscale, 1)
-    hshear_ = hshear + u(-opt.d_hshear, opt.d_hshear)
-    ty_ = ty + u(-opt.d_vtrans, opt.d_vtrans)
-    drot = opt.d_rotate * math.pi / 180
-    phi_ = phi + u(-drot, drot)
-    brightness_ = brightness + u(-opt.d_brightness, opt.d_brightness)
-    contrast_ = contrast * u(1 / opt.d_contrast, opt.d_contrast)
-    return np.stack([d_pos, d_neg, sx, sy, phi, tx, ty, hshear, brightness, contrast,
-                     sx_, sy, phi_, tx, ty_, hshear_, brightness_, contrast_], axis=-1).astype(np.float32)
-
-
-def _p(t):
-    return t.data_ptr()
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-class Trainer:
-    """Device state of a training run: images, nnz, permutation, parameters, momenta, workspace."""
-
-    def __init__(self, x0, x1, nnz, perm, layers, n_pairs, device):
-        import torch
-        self.lib = tl.load()
-        self.dev = device
-        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
+    def __init__(self, x0, x1, nnz, perm, conv_layers, fc_layers, n_pairs, device):
+        super().__init__(nnz, perm, conv_layers, fc_layers, n_pairs, device)
         x0, x1 = np.asarray(x0), np.asarray(x1)
         self.n_img, self.H, self.W = x0.shape[0], x0.shape[-2], x0.shape[-1]
-        self.x0 = f32(x0.reshape(self.n_img, self.H, self.W))
-        self.x1 = f32(x1.reshape(self.n_img, self.H, self.W))
-        self.nnz = f32(np.asarray(nnz).reshape(-1, 4))
-        self.perm = torch.from_numpy(np.ascontiguousarray(perm, np.int32)).to(device)
-        self.params = f32(flat_params(layers))
-        self.moms = torch.zeros_like(self.params)
-        self.n_pairs = n_pairs
-        self.ws_bytes = self.lib.mc_train_workspace_bytes(n_pairs)
-        if self.ws_bytes == 0:
-            raise ValueError("train: %d pairs per batch is outside libmctrain.so's range" % n_pairs)
-        self.ws = torch.empty(self.ws_bytes // 4 + 1, dtype=torch.float32, device=device)
+        self.x0 = self.f32(x0.reshape(self.n_img, self.H, self.W))
+        self.x1 = self.f32(x1.reshape(self.n_img, self.H, self.W))
+
+
+class Trainer(KittiTrainer):
+    """Device state of a training run: images, nnz, permutation, parameters, momenta, workspace."""
+    LIB, WHO, SHAPE = tl, "train", NET
+
+    def __init__(self, x0, x1, nnz, perm, layers, n_pairs, device):
+        super().__init__(x0, x1, nnz, perm, layers, (), n_pairs, device)
 
     def run(self, t0, prm, lr, mom, margin, pow_, losses):
         """mc_train_run: prm (n_steps, n_pairs, 18) on the device; losses (>= n_steps) device float32."""
-        n_steps = prm.shape[0]
-        tl.check(self.lib.mc_train_run(_p(self.x0), _p(self.x1), self.n_img, self.H, self.W, _p(self.nnz), self.nnz.shape[0],
-                                       _p(self.perm), self.perm.shape[0], t0, n_steps, self.n_pairs, _p(prm), _p(self.params),
-                                       _p(self.moms), lr, mom, margin, pow_, _p(losses), self.ws.data_ptr(), self.ws_bytes,
-                                       _stream()), "mc_train_run")
-
-    def layers(self):
-        return unflat_params(self.params.cpu().numpy())
+        self.call("run", _p(self.x0), _p(self.x1), self.n_img, self.H, self.W, _p(self.nnz), self.nnz.shape[0], _p(self.perm),
+                  self.perm.shape[0], t0, prm.shape[0], self.n_pairs, _p(prm), _p(self.params), _p(self.moms), lr, mom, margin,
+                  pow_, _p(losses))
 
 
 def sample(x0, x1, nnz, rows, prm):
@@ -189,16 +126,7 @@ def sample(x0, x1, nnz, rows, prm):
 def step_batch(patches, params, moms, lr, mom, margin, pow_, workspace=None):
     """mc_train_step_batch: one SGD step on patches (n_pairs, 3, 9, 9); params / moms updated in place.  Returns the
     device scalar of the batch's mean loss."""
-    import torch
-    lib = tl.load()
-    n_pairs = patches.shape[0]
-    need = lib.mc_train_workspace_bytes(n_pairs)
-    if workspace is None:
-        workspace = torch.empty(need // 4 + 1, dtype=torch.float32, device=patches.device)
-    loss = torch.empty(1, dtype=torch.float32, device=patches.device)
-    tl.check(lib.mc_train_step_batch(_p(patches), n_pairs, _p(params), _p(moms), lr, mom, margin, pow_, _p(loss),
-                                     workspace.data_ptr(), workspace.numel() * 4, _stream()), "mc_train_step_batch")
-    return loss
+    return common.step_batch(tl, "train", patches, params, moms, (lr, mom, margin, pow_), workspace)
 
 
 def net_fname_of(dataset, arch, argv):
@@ -236,47 +164,16 @@ last_run = None   # the latest train() result: {"net_fname", "losses" (per step,
 def train(dataset, arch, opt, argv, device, data=None):
     """main.lua:602-890 for -a train_tr / train_all: returns the saved net's file name."""
     global last_run
-    import torch
     from .main import load_net
     if data is None:
         data = load_data(dataset, opt)
-    nnz = data["nnz_tr"] if opt.a == "train_tr" else np.concatenate([data["nnz_tr"], data["nnz_te"]], 0)
-    nnz = np.asarray(nnz, np.float32).reshape(-1, 4)
+    nnz, rng, perm = training_rows(opt, data)
     n_pairs = opt.bs // 2
-    rng = np.random.default_rng(opt.seed)
-    perm = rng.permutation(nnz.shape[0]).astype(np.int32)
-    layers = load_net("random:%d" % opt.seed, dataset, arch)
-    tr = Trainer(data["x0"], data["x1"], nnz, perm, layers, n_pairs, device)
-    steps = n_steps_per_epoch(nnz.shape[0], opt.bs)
-    if steps < 1:
-        raise SystemExit("train: %d training pairs, fewer than a batch of %d" % (nnz.shape[0], n_pairs))
-    budget = opt.max_steps if opt.max_steps > 0 else None
-    lr = opt.lr
-    all_losses = []
-    t_start = time.perf_counter()
-    losses = torch.empty(steps, dtype=torch.float32, device=device)
-    for epoch in range(1, opt.epochs + 1):
-        if budget is not None and budget <= 0:
-            break
-        if epoch == 12:
-            lr = lr / 10
-        n = steps if budget is None else min(steps, budget)
-        for s0 in range(0, n, CHUNK_STEPS):
-            k = min(CHUNK_STEPS, n - s0)
-            prm = torch.from_numpy(draw_params(rng, opt, k, n_pairs)).to(device)
-            tr.run(s0 * n_pairs, prm, lr, opt.mom, opt.m, opt.pow, losses[s0:])
-        ep = losses[:n].cpu().numpy().copy()   # synchronises: the epoch's steps are done
-        all_losses.append(ep)
-        ok = (ep >= 0) & (ep < 100)           # main.lua:861-866
-        for e in ep[~ok]:
-            print("WARNING! err=%f" % e)
-        print(epoch, float(ep[ok].mean()) if ok.any() else float("nan"), lr, time.perf_counter() - t_start)
-        if budget is not None:
-            budget -= n
-    opt.lr = lr
+    tr = Trainer(data["x0"], data["x1"], nnz, perm, load_net("random:%d" % opt.seed, dataset, arch), n_pairs, device)
+    losses, epochs = run_epochs(tr, rng, opt, n_steps_per_epoch(nnz.shape[0], opt.bs), n_pairs, device, CHUNK_STEPS,
+                                lambda s0, prm, lr, out: tr.run(s0 * n_pairs, prm, lr, opt.mom, opt.m, opt.pow, out))
     fname = save_net(net_fname_of(dataset, arch, argv), tr.layers(), opt)
-    last_run = {"net_fname": fname, "losses": np.concatenate(all_losses) if all_losses else np.zeros(0, np.float32),
-                "epochs": len(all_losses)}
+    last_run = {"net_fname": fname, "losses": losses, "epochs": epochs}
     return fname
 
 

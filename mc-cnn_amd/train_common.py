@@ -1,0 +1,285 @@
+"""The host side that the four trainable nets share: train.py (KITTI fast), train_slow.py (KITTI slow), train_mb.py
+(Middlebury fast) and train_mb_slow.py (Middlebury slow) keep what is theirs -- data, image store, `Trainer.run`'s argument
+list, the saved net -- and take from here
+
+  * the parser blocks (`new_parser`, `pipeline_prm`, `check_bs`) and the augmentation defaults,
+  * the augmentation draws and the epoch schedule (`draw_params`, `n_steps_per_epoch`, `training_rows`, `run_epochs`),
+  * the flat parameter layout of a net of l1 convolutions and, for arch slow, l2 + 1 Linears (`NetShape`),
+  * the device state common to every `Trainer` (`TrainerBase`) and the one-step wrapper (`step_batch`).
+
+Randomness: ONE `numpy.random.Generator(-seed)` draws the permutation (`training_rows`; once, the same every epoch) and
+then, chunk by chunk, the augmentation parameters (`run_epochs`) and whatever the chunk callback draws after them
+(Middlebury's sources).  That order is what makes a run bitwise reproducible for a given -seed.
+"""
+import argparse
+import math
+import os
+import time
+
+import numpy as np
+
+from .params import SM_SKIP, SM_TERMINATE
+
+# ---- flags -------------------------------------------------------------------------------------------------------------
+PIPELINE_FLAGS = (("L1", "cbca_i1", "cbca_i2", "sgm_i"),                                                      # int
+                  ("tau1", "pi1", "pi2", "sgm_q1", "sgm_q2", "alpha1", "tau_so", "blur_sigma", "blur_t"))     # float
+
+# main.lua:33-64: the augmentation, per dataset
+AUG_DEFAULTS = {
+    "kitti": dict(hflip=0, vflip=0, rotate=7, hscale=0.9, scale=1, trans=0, hshear=0.1, brightness=0.7, contrast=1.3,
+                  d_vtrans=0, d_rotate=0, d_hscale=1, d_hshear=0, d_brightness=0.3, d_contrast=1),
+    "mb": dict(hflip=0, vflip=0, rotate=28, hscale=0.8, scale=0.8, trans=0, hshear=0.1, brightness=1.3, contrast=1.1,
+               d_vtrans=1, d_rotate=3, d_hscale=0.9, d_hshear=0.3, d_brightness=0.7, d_contrast=1.1),
+}
+AUG_DEFAULTS["kitti2015"] = AUG_DEFAULTS["kitti"]
+
+
+def new_parser(dataset, arch, t, train_defaults):
+    """An ArgumentParser with the flags every command line of `main.py <dataset> <arch>` has: -net_fname, -gpu, the 13
+    pipeline flags with the defaults of table t, -sm_terminate / -sm_skip, -seed, the optimiser's flags with
+    train_defaults, the dataset's augmentation flags, -epochs and -max_steps.  The caller adds -a and its own."""
+    ap = argparse.ArgumentParser(prog="main.py %s %s" % (dataset, arch), prefix_chars="-")
+    ap.add_argument("-net_fname", default="random:42")
+    ap.add_argument("-gpu", type=int, default=1, help="1-based, as cutorch.setDevice (main.lua:16,342)")
+    for keys, kind in zip(PIPELINE_FLAGS, (int, float)):
+        for k in keys:
+            ap.add_argument("-" + k, type=kind, default=t[k])
+    ap.add_argument("-sm_terminate", default="", choices=sorted(SM_TERMINATE), help="main.lua:25")
+    ap.add_argument("-sm_skip", default="", choices=sorted(SM_SKIP), help="main.lua:26")
+    ap.add_argument("-seed", type=int, default=42)
+    for k, v in train_defaults.items():
+        ap.add_argument("-" + k, type=type(v), default=v)
+    for k, v in AUG_DEFAULTS[dataset].items():
+        ap.add_argument("-" + k, type=int if k in ("hflip", "vflip") else float, default=float(v) if k not in ("hflip", "vflip") else v)
+    ap.add_argument("-epochs", type=int, default=14, help="main.lua:777 runs 14")
+    ap.add_argument("-max_steps", type=int, default=0, help="stop training after this many steps in all (0: no limit)")
+    return ap
+
+
+def pipeline_prm(t, opt):
+    """The hyper-parameter table of the post-CNN pipeline: t with the 13 flags and the stage switches of opt."""
+    prm = dict(t)
+    prm["sm_terminate"], prm["sm_skip"] = opt.sm_terminate, opt.sm_skip   # make_params maps the stage names
+    for k in PIPELINE_FLAGS[0] + PIPELINE_FLAGS[1]:
+        prm[k] = getattr(opt, k)
+    return prm
+
+
+def check_bs(opt, who, where):
+    if opt.bs < 2 or opt.bs % 2:
+        raise SystemExit("%s: -bs %d: a batch is pairs of samples (%s)" % (who, opt.bs, where))
+
+
+# ---- draws and schedule ------------------------------------------------------------------------------------------------
+def n_steps_per_epoch(n, bs):
+    """`for t = 1, n - bs/2, bs/2` (main.lua:787)."""
+    return len(range(1, n - bs // 2 + 1, bs // 2))
+
+
+def draw_params(rng, opt, n_steps, n_pairs):
+    """The augmentation parameters of main.lua:790-814 for n_steps x n_pairs pairs, (n_steps, n_pairs, 18) float32 in the
+    order of include/mc_train.h.  Vectorised numpy draws: the distributions and flags of the reference, not its stream."""
+    sh = (n_steps, n_pairs)
+    u = lambda a, b: rng.uniform(a, b, sh)
+    assert opt.hscale <= 1 and opt.scale <= 1
+    assert opt.contrast >= 1 and opt.d_contrast >= 1
+    d_pos = u(-opt.true1, opt.true1)
+    d_neg = u(opt.false1, opt.false2)
+    d_neg = np.where(rng.uniform(0, 1, sh) < 0.5, -d_neg, d_neg)
+    s = u(opt.scale, 1)
+    sx, sy = s * u(opt.hscale, 1), s
+    if opt.hflip == 1:
+        sx = np.where(rng.uniform(0, 1, sh) < 0.5, -sx, sx)
+    if opt.vflip == 1:
+        sy = np.where(rng.uniform(0, 1, sh) < 0.5, -sy, sy)
+    hshear = u(-opt.hshear, opt.hshear)
+    tx, ty = u(-opt.trans, opt.trans), u(-opt.trans, opt.trans)
+    rot = opt.rotate * math.pi / 180
+    phi = u(-rot, rot)
+    brightness = u(-opt.brightness, opt.brightness)
+    contrast = u(1 / opt.contrast, opt.contrast)
+    sx_ = sx * u(opt.d_hscale, 1)
+    hshear_ = hshear + u(-opt.d_hshear, opt.d_hshear)
+    ty_ = ty + u(-opt.d_vtrans, opt.d_vtrans)
+    drot = opt.d_rotate * math.pi / 180
+    phi_ = phi + u(-drot, drot)
+    brightness_ = brightness + u(-opt.d_brightness, opt.d_brightness)
+    contrast_ = contrast * u(1 / opt.d_contrast, opt.d_contrast)
+    return np.stack([d_pos, d_neg, sx, sy, phi, tx, ty, hshear, brightness, contrast,
+                     sx_, sy, phi_, tx, ty_, hshear_, brightness_, contrast_], axis=-1).astype(np.float32)
+
+
+def training_rows(opt, data):
+    """(nnz, rng, perm): the pixel list of -a train_tr (nnz_tr) or train_all (nnz_tr .. nnz_te), the run's Generator(-seed)
+    and its first draw, the permutation of the rows (main.lua:657: drawn once, the same every epoch)."""
+    nnz = data["nnz_tr"] if opt.a == "train_tr" else np.concatenate([data["nnz_tr"], data["nnz_te"]], 0)
+    nnz = np.asarray(nnz, np.float32).reshape(-1, 4)
+    rng = np.random.default_rng(opt.seed)
+    return nnz, rng, rng.permutation(nnz.shape[0]).astype(np.int32)
+
+
+def run_epochs(trainer, rng, opt, steps, n_pairs, device, chunk_steps, run_chunk):
+    """main.lua:777-875: -epochs epochs of `steps` steps, enqueued in chunks of chunk_steps; lr / 10 from epoch 12; at most
+    -max_steps steps in all.  Per chunk the augmentation parameters are drawn from rng, then
+    `run_chunk(s0, prm, lr, losses)` draws what else the net needs and calls `trainer.run` for steps s0 .. s0 + len(prm) - 1
+    of the epoch, rows s0 * n_pairs on of the permutation, writing their losses to losses[0:].  Leaves the last learning
+    rate in opt.lr, as main.lua does.  Returns (every step's loss in order, float32; the number of epochs run)."""
+    import torch
+    if steps < 1:
+        raise SystemExit("train: %d training pairs, fewer than a batch of %d" % (len(trainer.perm), n_pairs))
+    budget = opt.max_steps if opt.max_steps > 0 else None
+    lr = opt.lr
+    all_losses = []
+    t_start = time.perf_counter()
+    losses = torch.empty(steps, dtype=torch.float32, device=device)
+    for epoch in range(1, opt.epochs + 1):
+        if budget is not None and budget <= 0:
+            break
+        if epoch == 12:
+            lr = lr / 10
+        n = steps if budget is None else min(steps, budget)
+        for s0 in range(0, n, chunk_steps):
+            k = min(chunk_steps, n - s0)
+            prm = torch.from_numpy(draw_params(rng, opt, k, n_pairs)).to(device)
+            run_chunk(s0, prm, lr, losses[s0:])
+        ep = losses[:n].cpu().numpy().copy()   # synchronises: the epoch's steps are done
+        all_losses.append(ep)
+        ok = (ep >= 0) & (ep < 100)           # main.lua:861-866
+        for e in ep[~ok]:
+            print("WARNING! err=%f" % e)
+        print(epoch, float(ep[ok].mean()) if ok.any() else float("nan"), lr, time.perf_counter() - t_start)
+        if budget is not None:
+            budget -= n
+    opt.lr = lr
+    return np.concatenate(all_losses) if all_losses else np.zeros(0, np.float32), len(all_losses)
+
+
+# ---- the net's parameters ----------------------------------------------------------------------------------------------
+class NetShape:
+    """The flat parameter buffer of a training library: l1 3x3 convolutions 1 -> fm -> .. -> fm and, where l2 > 0, the
+    Linears 2 fm -> nh2 (l2 times) -> 1, every tensor followed by its bias (w1 b1 .. fw1 fb1 ..: the order of the
+    library's header).  The fast nets have l2 = 0 and no Linear at all."""
+
+    def __init__(self, l1, fm, l2, nh2, nparams, library):
+        self.l1, self.fm, self.l2, self.nh2, self.nparams, self.library = l1, fm, l2, nh2, nparams, library
+
+    def conv_shapes(self):
+        return [(self.fm, 1 if i == 0 else self.fm, 3, 3) for i in range(self.l1)]
+
+    def fc_shapes(self):
+        dims = [2 * self.fm] + [self.nh2] * self.l2 + [1] if self.l2 else []
+        return [(dims[i + 1], dims[i]) for i in range(len(dims) - 1)]
+
+    def flat_params(self, conv_layers, fc_layers=()):
+        """[(w, b)] of the convolutions and [(w (out,in), b)] of the Linears -> one float32 vector."""
+        layers = list(conv_layers) + list(fc_layers)
+        want = self.conv_shapes() + self.fc_shapes()
+        got = [tuple(np.shape(w)) for w, _ in layers], [tuple(np.shape(b)) for _, b in layers]
+        if got != (want, [(s[0],) for s in want]):
+            fc = ", l2 %d, nh2 %d" % (self.l2, self.nh2) if self.l2 else ""
+            raise ValueError("net of weights %s and biases %s, %s trains l1 %d, fm %d%s on 1 input plane"
+                             % (got + (self.library, self.l1, self.fm, fc)))
+        out = np.concatenate([np.asarray(a, np.float32).ravel() for wb in layers for a in wb])
+        assert out.size == self.nparams
+        return out
+
+    def unflat_params(self, v):
+        """The inverse of flat_params: (conv_layers, fc_layers)."""
+        v = np.asarray(v, np.float32)
+        if v.size != self.nparams:
+            raise ValueError("%d floats, %s's net has %d" % (v.size, self.library, self.nparams))
+        out, o = [], 0
+        for shape in self.conv_shapes() + self.fc_shapes():
+            n = int(np.prod(shape))
+            out.append((v[o:o + n].reshape(shape).copy(), v[o + n:o + n + shape[0]].copy()))
+            o += n + shape[0]
+        return out[:self.l1], out[self.l1:]
+
+    def tensor_names(self):
+        """The tensors of the flat buffer with their sizes, in order."""
+        names = []
+        for prefix, shapes in (("", self.conv_shapes()), ("f", self.fc_shapes())):
+            for i, s in enumerate(shapes):
+                names += [("%sw%d" % (prefix, i + 1), int(np.prod(s))), ("%sb%d" % (prefix, i + 1), s[0])]
+        return names
+
+    def init_net(self, seed, gain=1.0):
+        """(conv_layers, fc_layers) drawn uniformly from +-gain/sqrt(fan_in): gain 1 is the range of
+        nn.SpatialConvolution:reset and nn.Linear:reset (the draws are numpy's, not Torch's stream)."""
+        rng = np.random.default_rng(seed)
+        nets = []
+        for shapes in (self.conv_shapes(), self.fc_shapes()):
+            layers = []
+            for s in shapes:
+                bound = gain / np.sqrt(np.prod(s[1:]))
+                layers.append((rng.uniform(-bound, bound, s).astype(np.float32), rng.uniform(-bound, bound, (s[0],)).astype(np.float32)))
+            nets.append(layers)
+        return nets[0], nets[1]
+
+
+# ---- the device side ---------------------------------------------------------------------------------------------------
+def _p(t):
+    return t.data_ptr()
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def new_workspace(tlib, who, n_pairs, device):
+    """(bytes, float32 tensor of exactly that size) of `<prefix>_workspace_bytes(n_pairs)`, which answers 0 outside the
+    library's range of n_pairs."""
+    import torch
+    nbytes = getattr(tlib.load(), tlib.PREFIX + "_workspace_bytes")(n_pairs)
+    if nbytes == 0:
+        top = " [1, %d]" % tlib.MAX_PAIRS if hasattr(tlib, "MAX_PAIRS") else ""
+        raise ValueError("%s: %d pairs per batch is outside %s's range%s" % (who, n_pairs, os.path.basename(tlib.LIB_PATH), top))
+    return nbytes, torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+class TrainerBase:
+    """Device state of a training run that every net has: nnz, permutation, parameters, momenta, workspace.  A subclass
+    names its library module (LIB), itself for the messages (WHO) and its NetShape (SHAPE), uploads its image store and
+    defines `run`."""
+    LIB = WHO = SHAPE = None
+
+    def __init__(self, nnz, perm, conv_layers, fc_layers, n_pairs, device):
+        import torch
+        self.lib = self.LIB.load()
+        self.dev = device
+        self.nnz = self.f32(np.asarray(nnz).reshape(-1, 4))
+        self.perm = torch.from_numpy(np.ascontiguousarray(perm, np.int32)).to(device)
+        self.params = self.f32(self.SHAPE.flat_params(conv_layers, fc_layers))
+        self.moms = torch.zeros_like(self.params)
+        self.n_pairs = n_pairs
+        self.ws_bytes, self.ws = new_workspace(self.LIB, self.WHO, n_pairs, device)
+
+    def f32(self, a):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.dev)
+
+    def call(self, name, *args):
+        """`<prefix>_<name>(*args, workspace, its bytes, the current stream)`, checked."""
+        name = "%s_%s" % (self.LIB.PREFIX, name)
+        self.LIB.check(getattr(self.lib, name)(*args, self.ws.data_ptr(), self.ws_bytes, _stream()), name)
+
+    def nets(self):
+        return self.SHAPE.unflat_params(self.params.cpu().numpy())
+
+    def layers(self):
+        return self.nets()[0]
+
+
+def step_batch(tlib, who, patches, params, moms, scalars, workspace=None):
+    """`<prefix>_step_batch`: one SGD step on patches (n_pairs, 3, ws, ws) with the library's scalars (lr, mom and, for the
+    fast nets, margin and pow); params / moms updated in place.  Returns the device scalar of the batch's loss."""
+    import torch
+    n_pairs = patches.shape[0]
+    if workspace is None:
+        _, workspace = new_workspace(tlib, who, n_pairs, patches.device)
+    loss = torch.empty(1, dtype=torch.float32, device=patches.device)
+    name = tlib.PREFIX + "_step_batch"
+    tlib.check(getattr(tlib.load(), name)(_p(patches), n_pairs, _p(params), _p(moms), *scalars, _p(loss), workspace.data_ptr(),
+                                          workspace.numel() * 4, _stream()), name)
+    return loss

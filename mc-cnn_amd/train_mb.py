@@ -2,8 +2,9 @@
 
 Middlebury's fast net is `-l1 5 -fm 64` (main.lua:271-272): five valid 3x3 convolutions on 11 x 11 patches, trained by
 libmctrainmb.so (include/mc_train_mb.h) in two kernels a step, enqueued chunk by chunk through `mc_train_mb_run`.  The
-epoch loop, the augmentation draws, the permutation, the saved net and the error measure are train.py's (`draw_params`,
-`n_steps_per_epoch`, `net_fname_of`, `save_net`, `error_rate`), which were written dataset-wide.
+flags' common blocks, the augmentation draws, the permutation, the epoch loop, the parameter layout and `step_batch` are
+train_common.py's, shared by all four nets; the saved net and the error measure are train.py's (`net_fname_of`, `save_net`,
+`error_rate`).
 
 What is Middlebury's own:
   * the image store is ragged: `x_<n>_<light>.bin` holds (n_exp, 2, 1, H_n, W_n) for light >= 2, every image with its own
@@ -12,24 +13,27 @@ What is Middlebury's own:
     per image;
   * the left patch of a pair comes from X[img][light][exp, 1], the right ones from X[img][light_][exp_, 2], where exp_ is
     redrawn with probability -d_exp and light_ = max(2, light - 1) with probability -d_light (main.lua:828-841):
-    `draw_sources` draws them, vectorised per chunk, and resolves them to the two plane ids of each pair;
+    `draw_sources` draws them, vectorised per chunk, and resolves them to the two plane ids of each pair (`chunk_sources`:
+    after the chunk's augmentation parameters, from the same Generator);
   * `test_te` predicts (te[i], 2) for every te, then (5, 3) and (5, 4), from light 1 of each image with that image's own
     disp_max (meta.bin), direction -1 only, err_at 1.
 
 The draws are the reference's distributions from one numpy Generator(-seed), not Torch's Mersenne-Twister stream (see
 train.py).  `preprocess_mb.py` is not part of this project: `-data_dir` (default data.mb.<rect>_<color>) has to hold its
-output.  `mb slow` trains through train_mb_slow.py.  Not covered: -color rgb, -a submit, -a test_all (main.lua:1136 asserts it
+output.  `mb slow` trains through train_mb_slow.py, which shares this module's flags (`parse_mb`), data, store
+(`MbTrainer`), source draws and `evaluate`.  Not covered: -color rgb, -a submit, -a test_all (main.lua:1136 asserts it
 away itself), -subset, -debug.
 """
-import argparse
 import os
 import time
 
 import numpy as np
 
 from . import _train_mb_lib as tml
+from . import train_common as common
 from .binio import fromfile
-from .train import draw_params, error_rate, n_steps_per_epoch, net_fname_of, save_net
+from .train import error_rate, net_fname_of, save_net
+from .train_common import _p, _stream, draw_params, n_steps_per_epoch, run_epochs, training_rows  # noqa: F401
 
 CHUNK_STEPS = 256           # steps enqueued per mc_train_mb_run call (one chunk of parameter and source draws)
 ACTIONS = ("train_tr", "train_all", "test_te")
@@ -38,64 +42,48 @@ MB_TRAIN_DEFAULTS = dict(m=0.2, pow=1, lr=0.002, bs=128, mom=0.9, true1=0.5, fal
 PLANE_DTYPE = np.dtype([("offset", "<i8"), ("H", "<i4"), ("W", "<i4")])   # mc_train_mb_plane
 
 
+def parse_mb(argv, arch, train_defaults, who):
+    """The flags of `main.lua mb <arch> -a train_tr | train_all | test_te` with main.lua's names and defaults, for
+    train_mb.parse (who = "train_mb") and train_mb_slow.parse.  Returns (dataset, arch, opt, prm) as main.parse does; prm has
+    left_only = 1 (outside -a predict dataset mb runs direction -1 only, main.lua:953-955)."""
+    from .params import TABLES
+    t = TABLES[("mb", arch)]
+    ap = common.new_parser("mb", arch, t, train_defaults)
+    ap.add_argument("-a", required=True)
+    ap.add_argument("-ds", type=int, default=2001, help="parsed and ignored: main.lua declares it (267 for arch fast) and never reads it")
+    ap.add_argument("-rect", default="imperfect", help="main.lua:68")
+    ap.add_argument("-color", default="gray", help="main.lua:69")
+    ap.add_argument("-data_dir", default="", help="default data.mb.<rect>_<color> (main.lua:456)")
+    ap.add_argument("-subset", type=float, default=1.0, help="main.lua:28; only 1 is supported")
+    ap.add_argument("-debug", action="store_true", help="main.lua:18; not supported")
+    opt = ap.parse_args(argv[2:])
+    if opt.a == "test_all":
+        raise SystemExit("%s: -a test_all is not supported on Middlebury (main.lua:1136 asserts the same)" % who)
+    if opt.a == "submit":
+        raise SystemExit("%s: -a submit is out of scope (it writes the Middlebury evaluation's PFM files)" % who)
+    if opt.a not in ACTIONS:
+        raise SystemExit("%s: -a %s is not a training or testing action; mb %s covers -a %s" % (who, opt.a, arch, " | ".join(ACTIONS)))
+    if opt.color != "gray":
+        raise SystemExit("%s: -color %s: the nets here have one input plane, only -color gray is supported" % (who, opt.color))
+    if opt.subset != 1:
+        raise SystemExit("%s: -subset %g is not supported (the whole training set is used)" % (who, opt.subset))
+    if opt.debug:
+        raise SystemExit("%s: -debug (main.lua:1240-1260 writes images of every prediction) is not supported" % who)
+    common.check_bs(opt, who, "main.lua:789")
+    prm = common.pipeline_prm(t, opt)
+    prm["left_only"] = 1
+    return "mb", arch, opt, prm
+
+
 def parse(argv):
-    """The flags of `main.lua mb fast -a train_tr | train_all | test_te` with main.lua's names and defaults.  Returns
-    (dataset, arch, opt, prm) as main.parse does; prm has left_only = 1 (outside -a predict dataset mb runs direction -1
-    only, main.lua:953-955)."""
-    from .main import AUG_DEFAULTS
-    from .params import SM_SKIP, SM_TERMINATE, TABLES
+    """`main.lua mb fast -a train_tr | train_all | test_te`: parse_mb with the fast net's optimiser values."""
     if len(argv) >= 2 and argv[0] == "mb" and argv[1] == "slow":
         raise SystemExit("train_mb: mb slow is not trained here: its net (l1 5, fm 112, l2 3) keeps 221 KB of activations per "
                          "pair, more than the one-workgroup-per-pair step of libmctrainmb.so can hold in a CU's LDS; "
                          "train_mb_slow.parse takes these command lines (libmctrainmbslow.so, one workgroup per patch)")
     if len(argv) < 2 or argv[0] != "mb" or argv[1] != "fast":
         raise SystemExit("train_mb: training and testing on Middlebury cover mb fast -a %s" % " | ".join(ACTIONS))
-    t = TABLES[("mb", "fast")]
-    ap = argparse.ArgumentParser(prog="main.py mb fast", prefix_chars="-")
-    ap.add_argument("-a", required=True)
-    ap.add_argument("-net_fname", default="random:42")
-    ap.add_argument("-gpu", type=int, default=1, help="1-based, as cutorch.setDevice (main.lua:16,342)")
-    for k in ("L1", "cbca_i1", "cbca_i2", "sgm_i"):
-        ap.add_argument("-" + k, type=int, default=t[k])
-    for k in ("tau1", "pi1", "pi2", "sgm_q1", "sgm_q2", "alpha1", "tau_so", "blur_sigma", "blur_t"):
-        ap.add_argument("-" + k, type=float, default=t[k])
-    ap.add_argument("-sm_terminate", default="", choices=sorted(SM_TERMINATE), help="main.lua:25")
-    ap.add_argument("-sm_skip", default="", choices=sorted(SM_SKIP), help="main.lua:26")
-    ap.add_argument("-seed", type=int, default=42)
-    for k, v in MB_TRAIN_DEFAULTS.items():
-        ap.add_argument("-" + k, type=type(v), default=v)
-    ap.add_argument("-ds", type=int, default=2001, help="parsed and ignored: main.lua:267 declares it and never reads it")
-    for k, v in AUG_DEFAULTS["mb"].items():
-        ap.add_argument("-" + k, type=int if k in ("hflip", "vflip") else float, default=float(v) if k not in ("hflip", "vflip") else v)
-    ap.add_argument("-rect", default="imperfect", help="main.lua:68")
-    ap.add_argument("-color", default="gray", help="main.lua:69")
-    ap.add_argument("-data_dir", default="", help="default data.mb.<rect>_<color> (main.lua:456)")
-    ap.add_argument("-subset", type=float, default=1.0, help="main.lua:28; only 1 is supported")
-    ap.add_argument("-debug", action="store_true", help="main.lua:18; not supported")
-    ap.add_argument("-epochs", type=int, default=14, help="main.lua:777 runs 14")
-    ap.add_argument("-max_steps", type=int, default=0, help="stop training after this many steps in all (0: no limit)")
-    opt = ap.parse_args(argv[2:])
-    if opt.a == "test_all":
-        raise SystemExit("train_mb: -a test_all is not supported on Middlebury (main.lua:1136 asserts the same)")
-    if opt.a == "submit":
-        raise SystemExit("train_mb: -a submit is out of scope (it writes the Middlebury evaluation's PFM files)")
-    if opt.a not in ACTIONS:
-        raise SystemExit("train_mb: -a %s is not a training or testing action; mb fast covers -a %s" % (opt.a, " | ".join(ACTIONS)))
-    if opt.color != "gray":
-        raise SystemExit("train_mb: -color %s: the nets here have one input plane, only -color gray is supported" % opt.color)
-    if opt.subset != 1:
-        raise SystemExit("train_mb: -subset %g is not supported (the whole training set is used)" % opt.subset)
-    if opt.debug:
-        raise SystemExit("train_mb: -debug (main.lua:1240-1260 writes images of every prediction) is not supported")
-    if opt.bs < 2 or opt.bs % 2:
-        raise SystemExit("train_mb: -bs %d: a batch is pairs of samples (main.lua:789)" % opt.bs)
-    prm = dict(t)
-    prm["sm_terminate"], prm["sm_skip"] = opt.sm_terminate, opt.sm_skip
-    for k in ("L1", "cbca_i1", "cbca_i2", "sgm_i", "tau1", "pi1", "pi2", "sgm_q1", "sgm_q2", "alpha1", "tau_so", "blur_sigma",
-              "blur_t"):
-        prm[k] = getattr(opt, k)
-    prm["left_only"] = 1
-    return "mb", "fast", opt, prm
+    return parse_mb(argv, "fast", MB_TRAIN_DEFAULTS, "train_mb")
 
 
 def data_dir_of(opt):
@@ -192,38 +180,15 @@ def draw_sources(rng, opt, img_ids, index):
 
 
 # ---- the net's parameters ----------------------------------------------------------------------------------------------
-def flat_params(layers):
-    """[(w, b)] of the five-layer net -> one float32 vector in include/mc_train_mb.h's order (w1 b1 .. w5 b5)."""
-    layers = list(layers)
-    want = [(tml.FM, 1 if i == 0 else tml.FM, 3, 3) for i in range(tml.L1)]
-    if [tuple(np.shape(w)) for w, _ in layers] != want or [tuple(np.shape(b)) for _, b in layers] != [(tml.FM,)] * tml.L1:
-        raise ValueError("net of shapes %s, libmctrainmb.so trains l1 5, fm 64 on 1 input plane" % ([tuple(np.shape(w)) for w, _ in layers],))
-    return np.concatenate([np.asarray(a, np.float32).ravel() for wb in layers for a in wb])
+NET = common.NetShape(tml.L1, tml.FM, 0, 0, tml.NPARAMS, "libmctrainmb.so")
+flat_params = NET.flat_params     # [(w, b)] of the five-layer net -> one float32 vector in include/mc_train_mb.h's order (w1 b1 .. w5 b5)
 
 
 def unflat_params(v):
-    v = np.asarray(v, np.float32)
-    if v.size != tml.NPARAMS:
-        raise ValueError("%d floats, Middlebury's fast net has %d" % (v.size, tml.NPARAMS))
-    layers, o = [], 0
-    for i in range(tml.L1):
-        cin = 1 if i == 0 else tml.FM
-        n = tml.FM * cin * 9
-        layers.append((v[o:o + n].reshape(tml.FM, cin, 3, 3).copy(), v[o + n:o + n + tml.FM].copy()))
-        o += n + tml.FM
-    return layers
+    return NET.unflat_params(v)[0]
 
 
 # ---- the device side -----------------------------------------------------------------------------------------------------
-def _p(t):
-    return t.data_ptr()
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
 def device_table(table, device):
     """PLANE_DTYPE records -> the device tensor mc_train_mb_* take (two int64 words per record)."""
     import torch
@@ -236,38 +201,30 @@ def device_table(table, device):
     return torch.from_numpy(table.view(np.int64).reshape(-1, 2).copy()).to(device)
 
 
-class Trainer:
+class MbTrainer(common.TrainerBase):
+    """TrainerBase and Middlebury's image store: the flat planes and their device_table."""
+
+    def __init__(self, planes, table, nnz, perm, conv_layers, fc_layers, n_pairs, device):
+        super().__init__(nnz, perm, conv_layers, fc_layers, n_pairs, device)
+        self.table = device_table(table, device)
+        self.planes = self.f32(planes)
+
+
+class Trainer(MbTrainer):
     """Device state of a training run: planes, table, nnz, permutation, parameters, momenta, workspace."""
+    LIB, WHO, SHAPE = tml, "train_mb", NET
 
     def __init__(self, planes, table, nnz, perm, layers, n_pairs, device):
-        import torch
-        self.lib = tml.load()
-        self.dev = device
-        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
-        self.table = device_table(table, device)
-        self.planes = f32(planes)
-        self.nnz = f32(np.asarray(nnz).reshape(-1, 4))
-        self.perm = torch.from_numpy(np.ascontiguousarray(perm, np.int32)).to(device)
-        self.params = f32(flat_params(layers))
-        self.moms = torch.zeros_like(self.params)
-        self.n_pairs = n_pairs
-        self.ws_bytes = self.lib.mc_train_mb_workspace_bytes(n_pairs)
-        if self.ws_bytes == 0:
-            raise ValueError("train_mb: %d pairs per batch is outside libmctrainmb.so's range [1, %d]" % (n_pairs, tml.MAX_PAIRS))
-        self.ws = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=device)
+        super().__init__(planes, table, nnz, perm, layers, (), n_pairs, device)
 
     def run(self, t0, src, prm, lr, mom, margin, pow_, losses):
         """mc_train_mb_run: src (n_steps, n_pairs, 2) int32 and prm (n_steps, n_pairs, 18) on the device; losses
         (>= n_steps) device float32."""
         n_steps = prm.shape[0]
         assert tuple(src.shape) == (n_steps, self.n_pairs, 2) and tuple(prm.shape) == (n_steps, self.n_pairs, tml.NPRM)
-        tml.check(self.lib.mc_train_mb_run(_p(self.planes), _p(self.table), self.table.shape[0], _p(self.nnz), self.nnz.shape[0],
-                                           _p(self.perm), self.perm.shape[0], t0, n_steps, self.n_pairs, _p(src), _p(prm),
-                                           _p(self.params), _p(self.moms), lr, mom, margin, pow_, _p(losses), self.ws.data_ptr(),
-                                           self.ws_bytes, _stream()), "mc_train_mb_run")
-
-    def layers(self):
-        return unflat_params(self.params.cpu().numpy())
+        self.call("run", _p(self.planes), _p(self.table), self.table.shape[0], _p(self.nnz), self.nnz.shape[0], _p(self.perm),
+                  self.perm.shape[0], t0, n_steps, self.n_pairs, _p(src), _p(prm), _p(self.params), _p(self.moms), lr, mom, margin,
+                  pow_, _p(losses))
 
 
 def sample(planes, table, nnz, rows, src, prm):
@@ -284,70 +241,41 @@ def sample(planes, table, nnz, rows, src, prm):
 def step_batch(patches, params, moms, lr, mom, margin, pow_, workspace=None):
     """mc_train_mb_step_batch: one SGD step on patches (n_pairs, 3, 11, 11); params / moms (148352,) updated in place.
     Returns the device scalar of the batch's mean loss."""
-    import torch
-    lib = tml.load()
-    n_pairs = patches.shape[0]
-    if workspace is None:
-        workspace = torch.empty(lib.mc_train_mb_workspace_bytes(n_pairs) // 4, dtype=torch.float32, device=patches.device)
-    loss = torch.empty(1, dtype=torch.float32, device=patches.device)
-    tml.check(lib.mc_train_mb_step_batch(_p(patches), n_pairs, _p(params), _p(moms), lr, mom, margin, pow_, _p(loss),
-                                         workspace.data_ptr(), workspace.numel() * 4, _stream()), "mc_train_mb_step_batch")
-    return loss
+    return common.step_batch(tml, "train_mb", patches, params, moms, (lr, mom, margin, pow_), workspace)
 
 
 # ---- training and testing ------------------------------------------------------------------------------------------------
 last_run = None   # the latest train() result: {"net_fname", "losses" (per step, float32), "epochs"}
 
 
-def train(opt, argv, device, data=None):
-    """main.lua:602-890 for mb fast, -a train_tr / train_all: returns the saved net's file name.  The loop is
-    train.train's (one permutation, drawn once; chunks of CHUNK_STEPS steps; lr / 10 from epoch 12; -max_steps), with the
-    pairs' sources drawn beside their augmentation parameters."""
-    global last_run
+def chunk_sources(rng, opt, nnz, perm, index, n_pairs, device):
+    """src_of(s0, k): the sources of steps s0 .. s0 + k - 1 of an epoch, drawn from rng for the images of those steps' pairs
+    in the permutation's order, as the (k, n_pairs, 2) int32 device tensor `run` takes."""
     import torch
+    img_of = nnz[perm, 0].astype(np.int64)
+
+    def src_of(s0, k):
+        ids = img_of[s0 * n_pairs:(s0 + k) * n_pairs].reshape(k, n_pairs)
+        return torch.from_numpy(draw_sources(rng, opt, ids, index)).to(device)
+    return src_of
+
+
+def train(opt, argv, device, data=None):
+    """main.lua:602-890 for mb fast, -a train_tr / train_all: returns the saved net's file name.  Every chunk's sources are
+    drawn after its augmentation parameters."""
+    global last_run
     from .main import load_net
     if data is None:
         data = load_mb_data(data_dir_of(opt), opt.a)
-    nnz = data["nnz_tr"] if opt.a == "train_tr" else np.concatenate([data["nnz_tr"], data["nnz_te"]], 0)
-    nnz = np.asarray(nnz, np.float32).reshape(-1, 4)
+    nnz, rng, perm = training_rows(opt, data)
     n_pairs = opt.bs // 2
-    rng = np.random.default_rng(opt.seed)
-    perm = rng.permutation(nnz.shape[0]).astype(np.int32)
-    img_of = nnz[perm, 0].astype(np.int64)      # the image of every pair of an epoch, in the permutation's order
-    layers = load_net("random:%d" % opt.seed, "mb", "fast")
-    tr = Trainer(data["planes"], data["table"], nnz, perm, layers, n_pairs, device)
-    steps = n_steps_per_epoch(nnz.shape[0], opt.bs)
-    if steps < 1:
-        raise SystemExit("train: %d training pairs, fewer than a batch of %d" % (nnz.shape[0], n_pairs))
-    budget = opt.max_steps if opt.max_steps > 0 else None
-    lr = opt.lr
-    all_losses = []
-    t_start = time.perf_counter()
-    losses = torch.empty(steps, dtype=torch.float32, device=device)
-    for epoch in range(1, opt.epochs + 1):
-        if budget is not None and budget <= 0:
-            break
-        if epoch == 12:
-            lr = lr / 10
-        n = steps if budget is None else min(steps, budget)
-        for s0 in range(0, n, CHUNK_STEPS):
-            k = min(CHUNK_STEPS, n - s0)
-            prm = torch.from_numpy(draw_params(rng, opt, k, n_pairs)).to(device)
-            ids = img_of[s0 * n_pairs:(s0 + k) * n_pairs].reshape(k, n_pairs)
-            src = torch.from_numpy(draw_sources(rng, opt, ids, data["index"])).to(device)
-            tr.run(s0 * n_pairs, src, prm, lr, opt.mom, opt.m, opt.pow, losses[s0:])
-        ep = losses[:n].cpu().numpy().copy()   # synchronises: the epoch's steps are done
-        all_losses.append(ep)
-        ok = (ep >= 0) & (ep < 100)           # main.lua:861-866
-        for e in ep[~ok]:
-            print("WARNING! err=%f" % e)
-        print(epoch, float(ep[ok].mean()) if ok.any() else float("nan"), lr, time.perf_counter() - t_start)
-        if budget is not None:
-            budget -= n
-    opt.lr = lr
+    src_of = chunk_sources(rng, opt, nnz, perm, data["index"], n_pairs, device)
+    tr = Trainer(data["planes"], data["table"], nnz, perm, load_net("random:%d" % opt.seed, "mb", "fast"), n_pairs, device)
+    losses, epochs = run_epochs(tr, rng, opt, n_steps_per_epoch(nnz.shape[0], opt.bs), n_pairs, device, CHUNK_STEPS,
+                                lambda s0, prm, lr, out: tr.run(s0 * n_pairs, src_of(s0, prm.shape[0]), prm, lr, opt.mom, opt.m,
+                                                                opt.pow, out))
     fname = save_net(net_fname_of("mb", "fast", argv), tr.layers(), opt)
-    last_run = {"net_fname": fname, "losses": np.concatenate(all_losses) if all_losses else np.zeros(0, np.float32),
-                "epochs": len(all_losses)}
+    last_run = {"net_fname": fname, "losses": losses, "epochs": epochs}
     return fname
 
 

@@ -48,13 +48,14 @@ def test_parse_overrides():
 
 
 def test_main_routes_mb_fast_training_and_main_parse_keeps_refusing():
+    from mc_cnn_amd import train_mb_slow
+    route = mcmain.training_module
     for a in ("train_tr", "train_all", "test_te"):
-        assert mcmain.trains_mb(["mb", "fast", "-a", a]) and mcmain.trains_mb(["mb", "fast", "-seed", "3", "-a", a, "-bs", "64"])
-    for argv in (["mb", "slow", "-a", "train_tr"], ["mb", "fast", "-a", "predict"], ["mb", "fast", "-a", "time"],
-                 ["kitti", "fast", "-a", "train_tr"], ["mb", "fast", "-a", "test_all"], ["mb", "fast", "-a", "submit"], ["mb", "fast"],
-                 ["mb", "fast", "-a"]):
-        assert not mcmain.trains_mb(argv), argv
-    assert not mcmain.trains_slow(["mb", "fast", "-a", "train_tr"])
+        assert route(["mb", "fast", "-a", a]) is tm and route(["mb", "fast", "-seed", "3", "-a", a, "-bs", "64"]) is tm
+    assert route(["mb", "slow", "-a", "train_tr"]) is train_mb_slow
+    for argv in (["mb", "fast", "-a", "predict"], ["mb", "fast", "-a", "time"], ["kitti", "fast", "-a", "train_tr"],
+                 ["mb", "fast", "-a", "test_all"], ["mb", "fast", "-a", "submit"], ["mb", "fast"], ["mb", "fast", "-a"]):
+        assert route(argv) is None, argv
     with pytest.raises(SystemExit, match="fast only"):
         mcmain.parse(["mb", "fast", "-a", "train_tr"])
     with pytest.raises(SystemExit, match="train_mb.parse"):

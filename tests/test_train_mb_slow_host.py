@@ -1,5 +1,5 @@
-"""CPU: the host side of `mb slow -a train_tr | train_all | test_te` (main.lua:116-130, 602-890): flags and routing (the new
-router beside the old ones, which keep refusing `mb slow`), the flat parameter layout and the saved net, libmctrainmbslow.so's
+"""CPU: the host side of `mb slow -a train_tr | train_all | test_te` (main.lua:116-130, 602-890): flags and routing (one
+routing table; the other parsers keep refusing `mb slow`), the flat parameter layout and the saved net, libmctrainmbslow.so's
 symbols, constants, workspace sizes, argument checks and kernel inventory, and the host loop of `train_mb_slow.train` with a
 recording stand-in for its Trainer."""
 import os
@@ -74,10 +74,10 @@ def test_parse_has_no_margin_and_no_pow(flag):
 
 
 def test_main_routes_mb_slow_training_and_the_old_routes_keep_refusing_it():
+    route = mcmain.training_module
     for a in ("train_tr", "train_all", "test_te"):
-        assert mcmain.trains_mb_slow(["mb", "slow", "-a", a]) and mcmain.trains_mb_slow(["mb", "slow", "-seed", "3", "-a", a, "-bs", "64"])
-        # the other routers and parsers refuse these command lines as before
-        assert not mcmain.trains_slow(["mb", "slow", "-a", a]) and not mcmain.trains_mb(["mb", "slow", "-a", a])
+        # to train_mb_slow and so to neither train_slow nor train_mb, whose parsers refuse these command lines as before
+        assert route(["mb", "slow", "-a", a]) is tms and route(["mb", "slow", "-seed", "3", "-a", a, "-bs", "64"]) is tms
         with pytest.raises(SystemExit, match="fast only"):
             mcmain.parse(["mb", "slow", "-a", a])
         with pytest.raises(SystemExit, match="train_mb.parse"):
@@ -86,13 +86,13 @@ def test_main_routes_mb_slow_training_and_the_old_routes_keep_refusing_it():
             tm.parse(["mb", "slow", "-a", a])
         with pytest.raises(SystemExit):
             ts.parse(["mb", "slow", "-a", a])
-    # everything the other routers take, and what no router takes
-    for argv in (["mb", "fast", "-a", "train_tr"], ["mb", "fast", "-a", "test_te"], ["kitti", "slow", "-a", "train_tr"],
-                 ["kitti2015", "slow", "-a", "test_all"], ["kitti", "fast", "-a", "train_tr"], ["mb", "slow", "-a", "predict"],
-                 ["mb", "slow", "-a", "time"], ["mb", "slow", "-a", "test_all"], ["mb", "slow", "-a", "submit"], ["mb", "slow"],
-                 ["mb", "slow", "-a"], ["mb", "census", "-a", "train_tr"]):
-        assert not mcmain.trains_mb_slow(argv), argv
-    assert mcmain.trains_mb(["mb", "fast", "-a", "train_tr"]) and mcmain.trains_slow(["kitti", "slow", "-a", "train_tr"])
+    # everything that routes to the other modules, and what routes to none
+    for argv, want in ((["mb", "fast", "-a", "train_tr"], tm), (["mb", "fast", "-a", "test_te"], tm), (["kitti", "slow", "-a", "train_tr"], ts),
+                       (["kitti2015", "slow", "-a", "test_all"], ts), (["kitti", "fast", "-a", "train_tr"], None),
+                       (["mb", "slow", "-a", "predict"], None), (["mb", "slow", "-a", "time"], None), (["mb", "slow", "-a", "test_all"], None),
+                       (["mb", "slow", "-a", "submit"], None), (["mb", "slow"], None), (["mb", "slow", "-a"], None),
+                       (["mb", "census", "-a", "train_tr"], None)):
+        assert route(argv) is want, argv
     assert "train_mb_slow" in str(pytest.raises(SystemExit, tm.parse, ["mb", "slow", "-a", "train_tr"]).value)
 
 

@@ -57,10 +57,13 @@ def test_parse_refuses_what_is_out_of_scope(argv):
 
 
 def test_main_routes_only_slow_training_and_main_parse_keeps_refusing():
-    assert mcmain.trains_slow(["kitti", "slow", "-a", "train_tr"]) and mcmain.trains_slow(["kitti2015", "slow", "-seed", "3", "-a", "test_all"])
-    for argv in (["mb", "slow", "-a", "train_tr"], ["kitti", "slow", "-a", "submit"], ["kitti", "slow", "-a", "predict"],
-                 ["kitti", "fast", "-a", "train_tr"], ["kitti", "slow"], ["kitti", "slow", "-a"]):
-        assert not mcmain.trains_slow(argv), argv
+    from mc_cnn_amd import train_mb_slow
+    route = mcmain.training_module
+    assert route(["kitti", "slow", "-a", "train_tr"]) is ts and route(["kitti2015", "slow", "-seed", "3", "-a", "test_all"]) is ts
+    assert route(["mb", "slow", "-a", "train_tr"]) is train_mb_slow          # not train_slow's: Middlebury's own accurate net
+    for argv in (["kitti", "slow", "-a", "submit"], ["kitti", "slow", "-a", "predict"], ["kitti", "fast", "-a", "train_tr"],
+                 ["kitti", "slow"], ["kitti", "slow", "-a"]):
+        assert route(argv) is None, argv
     for argv in (["mb", "slow", "-a", "train_tr"], ["kitti", "slow", "-a", "submit"], ["kitti", "slow", "-a", "train_tr"]):
         with pytest.raises(SystemExit, match="fast only"):
             mcmain.parse(argv)

@@ -14,8 +14,11 @@ int transpose(const float *in, float *out, int64_t R, int64_t Cn, int64_t ldin, 
 int fix_border(float *vol, int D, int H, int W, int n, int direction, hipStream_t st);
 int argmin_dhw(const float *vol, float *out, int D, int H, int W, int base1, hipStream_t st);
 int outlier_detection(const float *d0, const float *d1, float *outlier, int H, int W, int disp_max, hipStream_t st);
-int interpolate_occlusion(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st);
-int interpolate_mismatch(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st);
+// mask: one bit per pixel, set where outlier == 2 (word p >> 5, bit p & 31 of the flat pixel index p; (H*W + 31) / 32 words): written by
+// interpolate_occlusion, read by interpolate_mismatch, which walks its rays on an LDS copy of it where the image has at most 524288 pixels
+constexpr int MC_MIS_MASK_MAX_PIXELS = 524288;   // a 64 KiB mask
+int interpolate_occlusion(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st, unsigned *mask = nullptr);
+int interpolate_mismatch(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st, const unsigned *mask = nullptr);
 int subpixel(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st);
 int median2d(const float *img, float *out, int H, int W, int k, hipStream_t st);
 int mean2d(const float *img, const float *kernel, float *out, int H, int W, int ks, float alpha2, hipStream_t st);
@@ -83,7 +86,7 @@ struct Plan {
 	size_t cplan_bytes;     // per direction: the tile kernel's plan (cbca_tile.hip), 0 where it would not be reused
 	size_t total;
 	void *maps, *packed;
-	float *x0c, *x1c, *img[6], *gk;
+	float *x0c, *x1c, *img[6], *gk;   // gk: unused (the Gaussian table has its own device memory); kept so that the layout stays
 	float *bufA[2], *bufB[2], *bufC[2];   // ping-pong per side; bufC: scratch of the SGM's concurrent second direction and of pairs of CBCA passes
 	void *cplan[2];             // null where the direction has none
 };

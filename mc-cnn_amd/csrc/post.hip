@@ -2,6 +2,8 @@
 // Each kernel cites the adcensus.cu kernel whose arithmetic it reproduces.
 #include "launchers.h"
 
+#include <atomic>
+
 namespace mc {
 
 // ---- fill / scale / transposes ---------------------------------------------------
@@ -239,8 +241,42 @@ __global__ void __launch_bounds__(256) outlier_rows_kernel(const float *__restri
 	}
 }
 
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to (function, device): set at a kernel's first launch on a device, from whichever thread
+// gets there (setting it twice is harmless, so the flags need no lock, only to be atomic); cus: the device's CU count, fetched with it.
+struct LdsRaised {
+	std::atomic<int> cus[64] = {};                   // 0: not raised yet on this device
+	int raise(const void *kernel, int bytes, const char *who, int *ncu = nullptr)
+	{
+		int dev = 0;
+		hipError_t e = hipGetDevice(&dev);
+		if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+		if (e != hipSuccess) {
+			set_error("%s: hipGetDevice: %s (device %d)", who, hipGetErrorString(e), dev);
+			return (int)e;
+		}
+		int n = cus[dev].load(std::memory_order_acquire);
+		if (!n) {
+			e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+			if (e == hipSuccess) e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+			if (e != hipSuccess || n <= 0) {
+				set_error("%s: %d bytes of dynamic LDS on device %d: %s", who, bytes, dev, hipGetErrorString(e));
+				return e != hipSuccess ? (int)e : MC_EINVAL;
+			}
+			cus[dev].store(n, std::memory_order_release);
+		}
+		if (ncu) *ncu = n;
+		return 0;
+	}
+};
+
 int outlier_detection(const float *d0, const float *d1, float *outlier, int H, int W, int disp_max, hipStream_t st)
 {
+	MC_REQUIRE(W <= 160 * 1024, "outlier_detection: a row of %d pixels needs more than the 160 KiB of LDS its marks live in", W);
+	if (W > 64 * 1024) {   // beyond the default limit of dynamic LDS: raised once per device to all a CU has
+		static LdsRaised raised;
+		const int rc = raised.raise((const void *)outlier_rows_kernel, 160 * 1024, "outlier_detection");
+		if (rc) return rc;
+	}
 	hipLaunchKernelGGL(outlier_rows_kernel, dim3(H), dim3(256), (size_t)W, st, d0, d1, outlier, W, disp_max);
 	return check_launch("outlier_detection");
 }
@@ -250,13 +286,25 @@ int outlier_detection(const float *d0, const float *d1, float *outlier, int H, i
 // has none to its left, the reference's second scan finds the first one to the right, which is then the first valid
 // pixel of the row.  Both are row scans: one block per row, each thread owns a short run of pixels, the "last valid
 // index so far" is carried across threads by a max-scan in LDS.
+// mask (optional): one bit per pixel of the whole image, set where outlier == 2, bit (p & 31) of word p >> 5 for the flat pixel index p
+// -- what the mismatch ray walk tests.  A word is written, whole and once, by the block in whose row its first pixel lies (a row
+// does not end on a word boundary unless W % 32 == 0, so the block reads on into the following rows).
 __global__ void __launch_bounds__(256) interp_occ_rows_kernel(const float *__restrict__ d0, const float *__restrict__ outlier,
-                                                              float *__restrict__ out, int W)
+                                                              float *__restrict__ out, int W, unsigned *__restrict__ mask, int size)
 {
 	__shared__ int carry[256];
 	__shared__ int first_valid;
 	const int y = blockIdx.x, t = threadIdx.x;
 	const int64_t row = (int64_t)y * W;
+	if (mask) {
+		const int wa = (int)((row + 31) >> 5), wb = (int)((row + W + 31) >> 5);   // words whose first pixel lies in this row
+		for (int w0 = wa; w0 < wb; w0 += 8) {                                      // 256 threads = 8 words
+			const int p = w0 * 32 + t;
+			const uint64_t bal = __ballot(p < size && outlier[p] == 2);
+			const int w = w0 + (t >> 5);
+			if ((t & 31) == 0 && w < wb) mask[w] = (unsigned)(bal >> (t & 32));
+		}
+	}
 	const int seg = (W + 255) / 256;
 	const int xa = t * seg, xb = min(W, xa + seg);
 	if (t == 0) first_valid = W;
@@ -293,9 +341,10 @@ __global__ void __launch_bounds__(256) interp_occ_rows_kernel(const float *__res
 	}
 }
 
-int interpolate_occlusion(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st)
+int interpolate_occlusion(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st, unsigned *mask)
 {
-	hipLaunchKernelGGL(interp_occ_rows_kernel, dim3(H), dim3(256), 0, st, d0, outlier, out, W);
+	if (mask) MC_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), "interpolate_occlusion: %dx%d pixels do not fit the mask's 32-bit index", H, W);
+	hipLaunchKernelGGL(interp_occ_rows_kernel, dim3(H), dim3(256), 0, st, d0, outlier, out, W, mask, mask ? H * W : 0);
 	return check_launch("interpolate_occlusion");
 }
 
@@ -320,9 +369,154 @@ template <int K> __device__ __forceinline__ void ray_rank_step(float v, int inb,
 // without the float rounding sequence.  The mark is fetched through a buffer whose range check answers 0 ("not a mismatch")
 // for a position outside the image, so the loop has one exit test and no nested regions.
 #define MC_MIS_NU 4
-__global__ void __launch_bounds__(256) interp_mis_rays_kernel(const float *__restrict__ d0, const float *__restrict__ outlier,
-                                                              float *__restrict__ out, int size, int H, int W)
+constexpr int MIS_NT = 1024;                 // threads of a block of the mask path = pixels of a chunk
+constexpr unsigned MIS_OOB = 0x80000000u;
+
+// Rank selection among the 16 values of a DPP row: the lanes whose value has rank n / 2 in the ascending order of the n rays that ended
+// inside the image (inb) write it; no such ray: lane 0 of the row keeps d0.
+__device__ __forceinline__ void ray_select(float v, int inb, int ray, int id, const float *__restrict__ d0, float *__restrict__ out)
 {
+	int less = 0, eq = inb;
+	ray_rank_step<1>(v, inb, less, eq); ray_rank_step<2>(v, inb, less, eq); ray_rank_step<3>(v, inb, less, eq);
+	ray_rank_step<4>(v, inb, less, eq); ray_rank_step<5>(v, inb, less, eq); ray_rank_step<6>(v, inb, less, eq);
+	ray_rank_step<7>(v, inb, less, eq); ray_rank_step<8>(v, inb, less, eq); ray_rank_step<9>(v, inb, less, eq);
+	ray_rank_step<10>(v, inb, less, eq); ray_rank_step<11>(v, inb, less, eq); ray_rank_step<12>(v, inb, less, eq);
+	ray_rank_step<13>(v, inb, less, eq); ray_rank_step<14>(v, inb, less, eq); ray_rank_step<15>(v, inb, less, eq);
+	const uint64_t bal = __ballot(inb != 0);
+	const int n = __builtin_popcount((unsigned)((bal >> ((threadIdx.x & 48))) & 0xffffu));
+	if (n == 0) {
+		if (ray == 0) out[id] = d0[id];
+		return;
+	}
+	const int want = n / 2;
+	if (inb && less <= want && want < less + eq) out[id] = v;   // lanes that qualify hold the same value
+}
+
+// With the mismatch marks as a bitmask (interp_occ_rows_kernel; at most MC_MIS_MASK_MAX_PIXELS pixels): one resident block per CU copies the
+// mask into LDS and takes the pixels [blockIdx.x * per, + per) in chunks of MIS_NT.  Per chunk: (a) every thread copies one pixel that is no
+// mismatch and the mismatches are listed; (b) the work items are (listed pixel, ray): a lane walks one item MC_MIS_NU positions per round and,
+// in the round in which its ray stops, leaves where in slot[item] and draws the next item from the chunk's counter -- no lane waits for a
+// longer ray, a wave ends when the items run out; (c) 16 lanes per listed pixel select as above.
+// Within a round the positions are q + o1, q + o2, q + o2 + o1, q + 2 o2 for the pixel index q of the (integer) start: two half-pixel steps
+// are a whole one, (sx, sy) pixels, and the odd step rounds to ((sx + 1) >> 1, (sy + 1) >> 1) -- (2 X + k sx + 1) >> 1 for X2 >= 0, and a
+// negative X2 is outside the image like every X2 > 2 W - 2.
+__device__ __forceinline__ void mis_rays_masked(const float *__restrict__ d0, const float *__restrict__ outlier, float *__restrict__ out,
+                                                int size, int H, int W, const unsigned *__restrict__ mask, int per)
+{
+	static_assert(MC_MIS_NU == 4, "the round below is two whole-pixel steps");
+	extern __shared__ unsigned mis_lds[];
+	__shared__ int wave_n[MIS_NT / 64];
+	__shared__ int next_item;
+	const int nw = (size + 31) >> 5;
+	unsigned *lmask = mis_lds;                        // [nw]
+	unsigned *slot = lmask + nw;                      // [MIS_NT * 16]: pixel index the ray of item i stopped at, MIS_OOB if it left the image
+	int *list_y = (int *)(slot + MIS_NT * 16);        // [MIS_NT]: row of the chunk's j-th mismatch pixel
+	unsigned short *list = (unsigned short *)(list_y + MIS_NT);   // [MIS_NT]: the pixel itself, relative to the chunk
+	const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+	const int pa = blockIdx.x * per, pb = min(size, pa + per);
+	if (pa >= pb) return;
+	for (int i = tid; i < nw; i += MIS_NT) lmask[i] = mask[i];
+	// (sx, sy) + 2 of ray k, four bits each: hx = {0, -1, -2, -2, -2, -2, -2, -1, 0, 1, 2, 2, 2, 2, 2, 1}, hy = {2, 2, 2, 1, 0, -1, -2, -2, -2, -2, -2, -1, 0, 1, 2, 2}
+	constexpr unsigned HX_LO = 0x10000012u, HX_HI = 0x34444432u, HY_LO = 0x00123444u, HY_HI = 0x44321000u;
+	const unsigned xmax2 = 2u * (unsigned)W - 2u, ymax2 = 2u * (unsigned)H - 2u;
+	for (int c0 = pa; c0 < pb; c0 += MIS_NT) {
+		// (a)
+		const int p = c0 + tid;
+		bool mis = false;
+		if (p < pb) {
+			const float v = d0[p];
+			mis = outlier[p] == 2;
+			if (!mis) out[p] = v;
+		}
+		const uint64_t bal = __ballot(mis);
+		if (lane == 0) wave_n[wid] = __builtin_popcountll(bal);
+		if (tid == 0) next_item = MIS_NT;             // the first MIS_NT items go to the threads in order
+		__syncthreads();                              // (the first time round: lmask is complete as well)
+		int base = 0, nlist = 0;
+#pragma unroll
+		for (int k = 0; k < MIS_NT / 64; ++k) {
+			const int c = wave_n[k];
+			base += k < wid ? c : 0;
+			nlist += c;
+		}
+		if (mis) {
+			const int j = base + __builtin_popcountll(bal & (((uint64_t)1 << lane) - 1));
+			list[j] = (unsigned short)tid;
+			list_y[j] = p / W;
+		}
+		__syncthreads();
+		// (b)
+		const int nitems = nlist * 16;
+		int i = tid;
+		int q = 0, X2 = 0, Y2 = 0, sx = 0, sy = 0, o1 = 0, o2 = 0;
+		auto start = [&]() {
+			const int j = i >> 4, ray = i & 15, sh = 4 * (ray & 7);
+			sx = (int)(((ray < 8 ? HX_LO : HX_HI) >> sh) & 15u) - 2;
+			sy = (int)(((ray < 8 ? HY_LO : HY_HI) >> sh) & 15u) - 2;
+			q = c0 + list[j];
+			const int y = list_y[j];
+			X2 = 2 * (q - y * W);
+			Y2 = 2 * y;
+			o1 = ((sy + 1) >> 1) * W + ((sx + 1) >> 1);
+			o2 = sy * W + sx;
+		};
+		if (i < nitems) start();
+		while (i < nitems) {
+			const int o[MC_MIS_NU] = {o1, o2, o2 + o1, 2 * o2};
+			unsigned off[MC_MIS_NU], m[MC_MIS_NU];
+#pragma unroll
+			for (int k = 0; k < MC_MIS_NU; ++k) {
+				X2 += sx;
+				Y2 += sy;
+				const bool in = (unsigned)X2 <= xmax2 && (unsigned)Y2 <= ymax2;
+				const unsigned a = in ? (unsigned)(q + o[k]) : 0u;   // (word 0 outside: the four reads of a round go out together, unconditionally)
+				off[k] = in ? a : MIS_OOB;
+				m[k] = lmask[a >> 5] >> (a & 31);
+				m[k] = in ? m[k] & 1u : 0u;
+			}
+			q += 2 * o2;
+			unsigned stop = MIS_OOB;
+			bool stopped = false;
+#pragma unroll
+			for (int k = MC_MIS_NU - 1; k >= 0; --k) {   // the first position that is no mismatch (or outside) wins
+				const bool hit = m[k] == 0;
+				stop = hit ? off[k] : stop;
+				stopped = hit ? true : stopped;
+			}
+			if (stopped) {
+				slot[i] = stop;
+				i = atomicAdd(&next_item, 1);
+				if (i < nitems) start();
+			}
+		}
+		__syncthreads();
+		// (c): the value of pass k + 1 is on its way while pass k ranks
+		const int ray = tid & 15;
+		int j = tid >> 4;
+		unsigned stop = j < nlist ? slot[j * 16 + ray] : MIS_OOB;
+		float v = d0[stop != MIS_OOB ? stop : 0u];       // (pixel 0 for a ray that left: an unconditional load can stay in flight)
+		while (j < nlist) {
+			const int jn = j + MIS_NT / 16;
+			const unsigned stop_n = jn < nlist ? slot[jn * 16 + ray] : MIS_OOB;
+			const float v_n = d0[stop_n != MIS_OOB ? stop_n : 0u];
+			ray_select(stop != MIS_OOB ? v : 0.0f, stop != MIS_OOB ? 1 : 0, ray, c0 + list[j], d0, out);
+			j = jn;
+			stop = stop_n;
+			v = v_n;
+		}
+		__syncthreads();                              // the lists and slot are rewritten by the next chunk
+	}
+}
+
+__global__ void __launch_bounds__(MIS_NT) interp_mis_rays_kernel(const float *__restrict__ d0, const float *__restrict__ outlier,
+                                                                 float *__restrict__ out, int size, int H, int W,
+                                                                 const unsigned *__restrict__ mask, int per)
+{
+	if (mask) {
+		mis_rays_masked(d0, outlier, out, size, H, W, mask, per);
+		return;
+	}
+	// The marks in global memory (no mask, or an image beyond its cap); blocks of 256 threads.
 	// direction (dx, dy) of ray k in half pixels, adcensus.cu:1013-1030:
 	// dx = {0, -.5, -1, -1, -1, -1, -1, -.5, 0, .5, 1, 1, 1, 1, 1, .5}, dy = {1, 1, 1, .5, 0, -.5, -1, -1, -1, -1, -1, -.5, 0, .5, 1, 1}
 	const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -343,7 +537,7 @@ __global__ void __launch_bounds__(256) interp_mis_rays_kernel(const float *__res
 	int X2 = 2 * x, Y2 = 2 * y;
 	// The path does not depend on what it finds: the marks of the next MC_MIS_NU positions are requested together and tested in
 	// order, so a step costs a fraction of a memory round trip (the start pixel is a mismatch: the walk begins one step out).
-	constexpr unsigned OOB = 0x80000000u;
+	constexpr unsigned OOB = MIS_OOB;
 	unsigned stop = OOB;             // byte offset of the pixel the ray stops at, OOB if it left the image
 	for (bool go = true; go;) {
 		unsigned off[MC_MIS_NU], o[MC_MIS_NU];
@@ -367,28 +561,29 @@ __global__ void __launch_bounds__(256) interp_mis_rays_kernel(const float *__res
 	const int inb = stop != OOB ? 1 : 0;
 	const float v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, stop, 0, 0));   // 0 outside
 	// all 16 lanes of this pixel are here (mis is uniform over the row of 16)
-	int less = 0, eq = inb;
-	ray_rank_step<1>(v, inb, less, eq); ray_rank_step<2>(v, inb, less, eq); ray_rank_step<3>(v, inb, less, eq);
-	ray_rank_step<4>(v, inb, less, eq); ray_rank_step<5>(v, inb, less, eq); ray_rank_step<6>(v, inb, less, eq);
-	ray_rank_step<7>(v, inb, less, eq); ray_rank_step<8>(v, inb, less, eq); ray_rank_step<9>(v, inb, less, eq);
-	ray_rank_step<10>(v, inb, less, eq); ray_rank_step<11>(v, inb, less, eq); ray_rank_step<12>(v, inb, less, eq);
-	ray_rank_step<13>(v, inb, less, eq); ray_rank_step<14>(v, inb, less, eq); ray_rank_step<15>(v, inb, less, eq);
-	const uint64_t bal = __ballot(inb != 0);
-	const int n = __builtin_popcount((unsigned)((bal >> ((threadIdx.x & 48))) & 0xffffu));
-	if (n == 0) {
-		if (ray == 0) out[id] = d0[id];
-		return;
-	}
-	const int want = n / 2;
-	if (inb && less <= want && want < less + eq) out[id] = v;   // lanes that qualify hold the same value
+	ray_select(v, inb, ray, id, d0, out);
 }
 
-int interpolate_mismatch(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st)
+int interpolate_mismatch(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st, const unsigned *mask)
 {
 	const int64_t size = (int64_t)H * W;
 	MC_REQUIRE(size * 16 < ((int64_t)1 << 31), "interpolate_mismatch: %dx%d pixels x 16 rays do not fit a 32-bit index", H, W);
 	MC_REQUIRE(H < (1 << 24) && W < (1 << 24), "interpolate_mismatch: %dx%d: a side beyond the 24-bit row / column arithmetic of the ray walk", H, W);
-	hipLaunchKernelGGL(interp_mis_rays_kernel, dim3(cdiv(size * 16, 256)), dim3(256), 0, st, d0, outlier, out, (int)size, H, W);
+	if (mask && size <= MC_MIS_MASK_MAX_PIXELS) {
+		constexpr int MAX_LDS = MC_MIS_MASK_MAX_PIXELS / 8 + MIS_NT * (16 * 4 + 4 + 2);
+		static LdsRaised raised;
+		int cus = 0;
+		const int rc = raised.raise((const void *)interp_mis_rays_kernel, MAX_LDS, "interpolate_mismatch", &cus);
+		if (rc) return rc;
+		// one block per CU where the image has a chunk for each; a block's share is a multiple of 64 pixels
+		const int blocks = (int)min((int64_t)cus, (int64_t)cdiv(size, MIS_NT));
+		const int per = (int)(cdiv(size, blocks) + 63) / 64 * 64;
+		const size_t lds = (size_t)((size + 31) / 32) * 4 + MIS_NT * (16 * 4 + 4 + 2);
+		hipLaunchKernelGGL(interp_mis_rays_kernel, dim3(blocks), dim3(MIS_NT), lds, st, d0, outlier, out, (int)size, H, W, mask, per);
+		return check_launch("interpolate_mismatch");
+	}
+	hipLaunchKernelGGL(interp_mis_rays_kernel, dim3(cdiv(size * 16, 256)), dim3(256), 0, st, d0, outlier, out, (int)size, H, W,
+	                   (const unsigned *)nullptr, 0);
 	return check_launch("interpolate_mismatch");
 }
 
@@ -422,9 +617,9 @@ int subpixel(const float *d0, const float *vol, float *out, int D, int H, int W,
 
 // ---- median2d, adcensus.cu:1575-1594 ------------------------------------------------------------
 // xs[n/2] of the ascending sort of the in-bounds taps (no NaNs reach this stage, so any correct selection equals
-// the reference's selection sort).  Interior pixels of the 3x3 / 5x5 filters use forgetful selection in registers
-// (repeatedly drop the minimum and maximum of a working set of N/2+2 values, feeding in the rest: ~130 compare-
-// exchanges for N = 25); border pixels and larger kernels count ranks.
+// the reference's selection sort).  The 3x3 / 5x5 filters use forgetful selection in registers (repeatedly drop the
+// minimum and maximum of a working set of N/2+2 values, feeding in the rest: ~130 compare-exchanges for N = 25), a
+// window cut by the image edge after padding it with infinities; larger kernels count ranks.
 __device__ __forceinline__ void cswap(float &a, float &b)
 {
 	const float lo = fminf(a, b), hi = fmaxf(a, b);
@@ -480,13 +675,21 @@ __global__ void __launch_bounds__(256) median_kernel(const float *__restrict__ i
 	const int xa = max(0, x - KR), xb = min(W - 1, x + KR), ya = max(0, y - KR), yb = min(H - 1, y + KR);
 	const int n = (xb - xa + 1) * (yb - ya + 1);
 	if constexpr (KR == 1 || KR == 2) {
-		if (n == K * K) {  // interior pixel
-			float v[K * K];
+		float v[K * K];
 #pragma unroll
-			for (int i = 0; i < K * K; ++i) v[i] = tile[ly + i % K][lx + i / K];
-			out[(int64_t)y * W + x] = median_forgetful<K * K>(v);
-			return;
+		for (int i = 0; i < K * K; ++i) v[i] = tile[ly + i % K][lx + i / K];
+		if (n != K * K) {
+			// a window cut by the image edge: of its K*K - n missing taps, K*K/2 - n/2 become -INF and the others +INF, which puts rank
+			// n/2 of the n taps inside at rank K*K/2 of the padded set (both counts are >= 0 for every n >= 1)
+			int lo = K * K / 2 - n / 2;
+#pragma unroll
+			for (int i = 0; i < K * K; ++i) {
+				const int ix = x - KR + i / K, iy = y - KR + i % K;
+				if (ix < xa || ix > xb || iy < ya || iy > yb) v[i] = lo-- > 0 ? -__builtin_inff() : __builtin_inff();
+			}
 		}
+		out[(int64_t)y * W + x] = median_forgetful<K * K>(v);
+		return;
 	}
 	const int want = n / 2;
 	float res = 0;

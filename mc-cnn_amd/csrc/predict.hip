@@ -4,11 +4,12 @@
 
 #include <map>
 #include <mutex>
+#include <utility>
 
 namespace mc {
 
-// gaussian(sigma), main.lua:528-540, double on the host.  Cached per sigma in PINNED host memory (allocated once, never
-// freed), so that the per-call upload into the workspace is a true asynchronous copy that never sees its source disappear.
+// gaussian(sigma), main.lua:528-540, double on the host.  mc_predict reads it from DEVICE memory, cached per (device, sigma): allocated and
+// uploaded synchronously at first use (complete before any stream can be given it) and never freed; it depends on the preset alone.
 void gaussian_fill(double sigma, float *k)
 {
 	const int ks = gaussian_ks(sigma), kr = ks / 2;
@@ -20,24 +21,31 @@ void gaussian_fill(double sigma, float *k)
 		}
 	}
 }
-struct GaussianK { const float *data; size_t n; };
-static int gaussian_cached(double sigma, GaussianK &out)
+static int gaussian_cached(double sigma, const float *&out)
 {
 	static std::mutex mu;
-	static std::map<double, GaussianK> cache;
-	std::lock_guard<std::mutex> lk(mu);
-	auto it = cache.find(sigma);
-	if (it != cache.end()) { out = it->second; return 0; }
-	const int ks = gaussian_ks(sigma);
-	float *k = nullptr;
-	const hipError_t e = hipHostMalloc((void **)&k, (size_t)ks * ks * sizeof(float), hipHostMallocDefault);
+	static std::map<std::pair<int, double>, const float *> cache;
+	int dev = 0;
+	hipError_t e = hipGetDevice(&dev);
 	if (e != hipSuccess) {
-		set_error("gaussian: hipHostMalloc: %s", hipGetErrorString(e));
+		set_error("gaussian: hipGetDevice: %s", hipGetErrorString(e));
 		return (int)e;
 	}
-	gaussian_fill(sigma, k);
-	out = GaussianK{k, (size_t)ks * ks};
-	cache[sigma] = out;
+	std::lock_guard<std::mutex> lk(mu);
+	auto it = cache.find({dev, sigma});
+	if (it != cache.end()) { out = it->second; return 0; }
+	const int ks = gaussian_ks(sigma);
+	std::vector<float> k((size_t)ks * ks);
+	gaussian_fill(sigma, k.data());
+	float *dk = nullptr;
+	e = hipMalloc((void **)&dk, k.size() * sizeof(float));
+	if (e == hipSuccess) e = hipMemcpy(dk, k.data(), k.size() * sizeof(float), hipMemcpyHostToDevice);
+	if (e != hipSuccess) {
+		set_error("gaussian: device table of %zu floats: %s", k.size(), hipGetErrorString(e));
+		if (dk) (void)hipFree(dk);
+		return (int)e;
+	}
+	out = cache[{dev, sigma}] = dk;
 	return 0;
 }
 
@@ -332,8 +340,15 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	};
 	if (p->lr_check) {
 		RUN(outlier_detection(d, dispv[1], outl, H, W, D, st));
-		RUN(stage(MC_SKIP_OCCLUSION, MC_SM_OCCLUSION, [&](float *o) { return interpolate_occlusion(d, outl, o, H, W, st); }));
-		RUN(stage(MC_SKIP_OCCLUSION, MC_SM_MISMATCH, [&](float *o) { return interpolate_mismatch(d, outl, o, H, W, st); }));
+		// the occlusion stage leaves the mismatch marks as a bitmask for the ray walk, in the cross arms' area (dead since the last
+		// aggregation pass); where that stage does not run there is none and the walk reads the marks themselves
+		const unsigned *mis_mask = nullptr;
+		RUN(stage(MC_SKIP_OCCLUSION, MC_SM_OCCLUSION, [&](float *o) {
+			unsigned *m = HW <= MC_MIS_MASK_MAX_PIXELS ? (unsigned *)pl.x0c : nullptr;
+			mis_mask = m;
+			return interpolate_occlusion(d, outl, o, H, W, st, m);
+		}));
+		RUN(stage(MC_SKIP_OCCLUSION, MC_SM_MISMATCH, [&](float *o) { return interpolate_mismatch(d, outl, o, H, W, st, mis_mask); }));
 	}
 	// subpixel on the LEFT volume (vol of the last loop iteration, main.lua:1068)
 	RUN(stage(MC_SKIP_SUBPIXEL, MC_SM_SUBPIXEL, [&](float *o) {
@@ -341,14 +356,9 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	}));
 	RUN(stage(MC_SKIP_MEDIAN, MC_SM_MEDIAN, [&](float *o) { return median2d(d, o, H, W, p->median_k, st); }));
 	if (sm_active && p->sm_skip != MC_SKIP_BILATERAL) {
-		GaussianK k;
-		RUN(gaussian_cached(p->blur_sigma, k));
-		const hipError_t e = hipMemcpyAsync(pl.gk, k.data, k.n * sizeof(float), hipMemcpyHostToDevice, st);  // pinned source
-		if (e != hipSuccess) {
-			set_error("mc_predict: kernel upload: %s", hipGetErrorString(e));
-			return (int)e;
-		}
-		RUN(mean2d(d, pl.gk, disp_out, H, W, gaussian_ks(p->blur_sigma), p->blur_t, st));
+		const float *gk = nullptr;
+		RUN(gaussian_cached(p->blur_sigma, gk));
+		RUN(mean2d(d, gk, disp_out, H, W, gaussian_ks(p->blur_sigma), p->blur_t, st));
 	} else {
 		RUN(scale(d, disp_out, HW, 1.0f, st));  // the last stage that ran is the result
 	}

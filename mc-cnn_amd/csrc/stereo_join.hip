@@ -389,16 +389,21 @@ __global__ void __launch_bounds__(64 * MC_JOIN_WPB) join_owner_kernel(const floa
 }
 
 // fix_border (main.lua:922-927) on (H,W,ds): the n outermost pixels of one side replicate the
-// (n+1)-th pixel's whole cost vector.  One wave per (row, border pixel).
-__global__ void __launch_bounds__(256) fix_border_hwd_kernel(float *__restrict__ vol, int D, int ds, int H, int W, int n,
-                                                             int direction)
+// (n+1)-th pixel's whole cost vector.  One wave per (volume, row, border pixel): the left volume's right border (direction -1),
+// then the right volume's left border (direction +1).
+__global__ void __launch_bounds__(256) fix_border_hwd_kernel(float *__restrict__ volL, float *__restrict__ volR, int D, int ds, int H,
+                                                             int W, int n)
 {
 	const int lane = threadIdx.x & 63;
-	const int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-	if (w >= (int64_t)H * n) return;
+	int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+	const int64_t per = (int64_t)H * n;
+	if (w >= 2 * per) return;
+	const bool right = w >= per;
+	if (right) w -= per;
+	float *vol = right ? volR : volL;
 	const int y = (int)(w / n), i = (int)(w % n) + 1;
-	const int dst = direction < 0 ? W - i : i - 1;
-	const int src = direction < 0 ? W - (n + 1) : n;
+	const int dst = right ? i - 1 : W - i;
+	const int src = right ? n : W - (n + 1);
 	const float *s = vol + ((int64_t)y * W + src) * ds;
 	float *t = vol + ((int64_t)y * W + dst) * ds;
 	for (int d = lane; d < D; d += 64) t[d] = s[d];
@@ -430,8 +435,7 @@ int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, 
 	}
 	const int rc = check_launch(what);
 	if (rc || n <= 0) return rc;
-	hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)H * n * 64, 256)), block, 0, st, volL, D, ds, H, W, n, -1);
-	hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)H * n * 64, 256)), block, 0, st, volR, D, ds, H, W, n, 1);
+	hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)2 * H * n * 64, 256)), block, 0, st, volL, volR, D, ds, H, W, n);
 	return check_launch("fix_border_hwd");
 }
 

@@ -23,6 +23,7 @@ INVENTORY = os.path.join(ROOT, "tests", "kernel_inventory.txt")
 INVENTORY_TRAIN_SLOW = os.path.join(ROOT, "tests", "kernel_inventory_train_slow.txt")   # libmctrainslow.so
 INVENTORY_TRAIN_MB = os.path.join(ROOT, "tests", "kernel_inventory_train_mb.txt")       # libmctrainmb.so
 INVENTORY_TRAIN_MB_SLOW = os.path.join(ROOT, "tests", "kernel_inventory_train_mb_slow.txt")   # libmctrainmbslow.so (shares the FC kernels' names with libmctrainslow.so)
+INVENTORY_EVAL = os.path.join(ROOT, "tests", "kernel_inventory_eval.txt")               # libmceval.so
 NAMESPACE = "mc::"
 
 
@@ -84,7 +85,7 @@ def launched(csv_paths):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("stats", nargs="+", help="kernel_stats.csv of rocprofv3 --kernel-trace --stats")
-    ap.add_argument("--inventory", nargs="+", default=[INVENTORY, INVENTORY_TRAIN_SLOW, INVENTORY_TRAIN_MB, INVENTORY_TRAIN_MB_SLOW])
+    ap.add_argument("--inventory", nargs="+", default=[INVENTORY, INVENTORY_TRAIN_SLOW, INVENTORY_TRAIN_MB, INVENTORY_TRAIN_MB_SLOW, INVENTORY_EVAL])
     a = ap.parse_args(argv)
     inv = {}
     for path in a.inventory:

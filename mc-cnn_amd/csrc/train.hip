@@ -22,6 +22,7 @@
 #include "../../include/mc_train.h"
 #include "train_sampler.h"
 #include "train_conv.h"
+#include "train_range.h"
 
 namespace mc {
 
@@ -224,8 +225,9 @@ int mc_train_run(const float *x0, const float *x1, int n_img, int H, int W, cons
 	if (int rc = check_step_args(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
 	MC_REQUIRE(perm && prm && losses, "train_run: null pointer");
 	MC_REQUIRE(n_steps >= 0, "train_run: n_steps %d", n_steps);
-	MC_REQUIRE(t0 >= 0 && t0 + (int64_t)n_steps * n_pairs <= n_perm, "train_run: steps [%lld, %lld) of the permutation exceed its %lld rows",
-	           (long long)t0, (long long)(t0 + (int64_t)n_steps * n_pairs), (long long)n_perm);
+	int64_t end;   // t0 + n_steps * n_pairs, saturated: train_range.h
+	MC_REQUIRE(train_steps_fit(t0, n_steps, n_pairs, n_perm, &end), "train_run: steps [%lld, %lld) of the permutation exceed its %lld rows",
+	           (long long)t0, (long long)end, (long long)n_perm);
 	if (int rc = prepare_step_kernels()) return rc;
 	const hipStream_t st = as_stream(stream);
 	for (int s = 0; s < n_steps; ++s) {

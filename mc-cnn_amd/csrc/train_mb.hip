@@ -24,6 +24,7 @@
 #include "../../include/mc_train_mb.h"
 #include "train_mb_sampler.h"   // sample_mb_pixel: a pair's patches from the ragged store, shared with train_mb_slow.hip
 #include "train_conv.h"
+#include "train_range.h"
 
 namespace mc {
 
@@ -239,8 +240,9 @@ int mc_train_mb_run(const float *planes, const mc_train_mb_plane *table, int n_p
 	if (int rc = check_step_args(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
 	MC_REQUIRE(perm && src && prm && losses, "train_mb_run: null pointer");
 	MC_REQUIRE(n_steps >= 0, "train_mb_run: n_steps %d", n_steps);
-	MC_REQUIRE(t0 >= 0 && t0 + (int64_t)n_steps * n_pairs <= n_perm, "train_mb_run: steps [%lld, %lld) of the permutation exceed its %lld rows",
-	           (long long)t0, (long long)(t0 + (int64_t)n_steps * n_pairs), (long long)n_perm);
+	int64_t end;   // t0 + n_steps * n_pairs, saturated: train_range.h
+	MC_REQUIRE(train_steps_fit(t0, n_steps, n_pairs, n_perm, &end), "train_mb_run: steps [%lld, %lld) of the permutation exceed its %lld rows",
+	           (long long)t0, (long long)end, (long long)n_perm);
 	if (int rc = prepare_step_kernels()) return rc;
 	const hipStream_t st = as_stream(stream);
 	for (int s = 0; s < n_steps; ++s) {

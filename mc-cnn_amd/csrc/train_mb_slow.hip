@@ -23,6 +23,7 @@
 #include "../../include/mc_train_mb_slow.h"
 #include "train_mb_sampler.h"
 #include "train_slow_conv.h"
+#include "train_range.h"
 #define MC_FC_HEAD_MAX_ROWS (2 * MC_TRAIN_MB_SLOW_MAX_PAIRS)
 #include "train_slow_fc.h"
 
@@ -309,8 +310,9 @@ int mc_train_mb_slow_run(const float *planes, const mc_train_mb_plane *table, in
 	if (int rc = check_step_args(n_pairs, params, moms, workspace, workspace_bytes)) return rc;
 	MC_REQUIRE(perm && src && prm && losses, "train_mb_slow_run: null pointer");
 	MC_REQUIRE(n_steps >= 0, "train_mb_slow_run: n_steps %d", n_steps);
-	MC_REQUIRE(t0 >= 0 && t0 + (int64_t)n_steps * n_pairs <= n_perm, "train_mb_slow_run: steps [%lld, %lld) of the permutation exceed its %lld rows",
-	           (long long)t0, (long long)(t0 + (int64_t)n_steps * n_pairs), (long long)n_perm);
+	int64_t end;   // t0 + n_steps * n_pairs, saturated: train_range.h
+	MC_REQUIRE(train_steps_fit(t0, n_steps, n_pairs, n_perm, &end), "train_mb_slow_run: steps [%lld, %lld) of the permutation exceed its %lld rows",
+	           (long long)t0, (long long)end, (long long)n_perm);
 	if (int rc = prepare_kernels()) return rc;
 	const hipStream_t st = as_stream(stream);
 	for (int s = 0; s < n_steps; ++s) {

@@ -26,6 +26,7 @@
 #include "mc_common.h"
 #include "../../include/mc_train_slow.h"
 #include "train_sampler.h"
+#include "train_range.h"
 #include "train_slow_conv.h"   // block_gemm and the three convolution GEMMs, here with a pair's three patches per workgroup
 #define MC_FC_HEAD_MAX_ROWS (2 * MC_TRAIN_SLOW_MAX_PAIRS)
 #include "train_slow_fc.h"     // fc_forward_kernel, fc_head_kernel, fc_backward_kernel, sgd_update
@@ -298,8 +299,9 @@ int mc_train_slow_run(const float *x0, const float *x1, int n_img, int H, int W,
 	if (int rc = check_step_args(n_pairs, params, moms, workspace, workspace_bytes)) return rc;
 	MC_REQUIRE(perm && prm && losses, "train_slow_run: null pointer");
 	MC_REQUIRE(n_steps >= 0, "train_slow_run: n_steps %d", n_steps);
-	MC_REQUIRE(t0 >= 0 && t0 + (int64_t)n_steps * n_pairs <= n_perm, "train_slow_run: steps [%lld, %lld) of the permutation exceed its %lld rows",
-	           (long long)t0, (long long)(t0 + (int64_t)n_steps * n_pairs), (long long)n_perm);
+	int64_t end;   // t0 + n_steps * n_pairs, saturated: train_range.h
+	MC_REQUIRE(train_steps_fit(t0, n_steps, n_pairs, n_perm, &end), "train_slow_run: steps [%lld, %lld) of the permutation exceed its %lld rows",
+	           (long long)t0, (long long)end, (long long)n_perm);
 	if (int rc = prepare_kernels()) return rc;
 	const hipStream_t st = as_stream(stream);
 	for (int s = 0; s < n_steps; ++s) {

@@ -1,8 +1,10 @@
-// The convolution GEMMs of the fast architecture's training step on v_mfma_f32_32x32x2_f32, shared by train.hip (four layers
-// on 9 x 9 patches) and train_mb.hip (five layers on 11 x 11 patches): 64 feature maps, a pair's three patches in LDS, one
-// workgroup of eight waves.  See train.hip's head for the three GEMMs.
+// The fast architecture's training step on v_mfma_f32_32x32x2_f32, shared by train.hip (four layers on 9 x 9 patches) and
+// train_mb.hip (five layers on 11 x 11 patches): 64 feature maps, a pair's three patches in LDS, one workgroup of eight waves.
+// The block GEMM, the three convolution GEMMs (see train.hip's head), the Normalize2 / StereoJoin1 / Margin2 tail, then the
+// step itself over a net N of train_net.h -- the LDS layout, the layer chain, the update -- and the step's argument check.
 #pragma once
 #include "mc_common.h"
+#include "train_net.h"
 
 namespace mc {
 
@@ -19,6 +21,10 @@ constexpr int SPLIT_FLOATS = NW * 16 * 64;   // LDS floats of the split-K partia
 // slices over the waves; the partial tiles meet in LDS and are added in slice order.
 // mac(acc, i, j, h, s0, s1): run K steps [s0, s1) for output row i / column j on lane half h.
 // out(row, col, v): the epilogue of one element.
+// A GEMM of N <= 32 columns has only two output tiles for eight waves: split_k(N) slices its K over four waves each.  N is
+// 3 * (output pixels) in the forward pass and 3 * (input pixels) in the data gradient; the weight gradient's 576 columns never split.
+__host__ __device__ constexpr int split_k(int N) { return N <= 32 ? 4 : 1; }
+
 template <int KS, class Mac, class Out>
 __device__ __forceinline__ void block_gemm(int N, int ksteps, float *split, Mac mac, Out out)
 {
@@ -193,6 +199,92 @@ __device__ __forceinline__ float hinge_tail(float *A, int c, float margin, int p
 		A[p * FM + c] = (n[p] - x[p] * x[p]) / denom * go[p] - others * x[p] / denom;
 	}
 	return loss;
+}
+
+// ---- the step of a net N -----------------------------------------------------------------------------------------------
+// LDS (floats): the activations of train_net.h, then the split-K partial tiles [8][16][64]
+template <class N> constexpr int STEP_LDS_FLOATS = lds_act<N>(N::NL + 1) + SPLIT_FLOATS;
+template <class N> constexpr size_t STEP_LDS_BYTES = (size_t)STEP_LDS_FLOATS<N> * sizeof(float);
+
+// layers L .. NL of the forward pass: A_l = ReLU(b_l + W_l * A_{l-1}), the last without ReLU; a barrier after each
+template <class N, int L = 1>
+__device__ __forceinline__ void chain_forward(const float *__restrict__ params, float *lds, float *split)
+{
+	constexpr int SI = side<N>(L - 1), SO = SI - 2;
+	conv_forward<L == 1 ? 1 : FM, SI, split_k(3 * SO * SO)>(params + off_w<N>(L), params + off_b<N>(L), lds + lds_act<N>(L - 1), lds + lds_act<N>(L),
+	                                                         L < N::NL, split);
+	__syncthreads();
+	if constexpr (L < N::NL) chain_forward<N, L + 1>(params, lds, split);
+}
+
+// layers L .. 1 of the backward pass, A_L holding its gradient: layer l's weight and bias gradients into g, then its data
+// gradient over A_{l-1} in place; a barrier between any two GEMMs
+template <class N, int L = N::NL>
+__device__ __forceinline__ void chain_backward(const float *__restrict__ params, float *__restrict__ g, float *lds, float *split)
+{
+	constexpr int SI = side<N>(L - 1);
+	conv_weight_grad<L == 1 ? 1 : FM, SI>(lds + lds_act<N>(L), lds + lds_act<N>(L - 1), g + off_w<N>(L), g + off_b<N>(L), split);
+	if constexpr (L > 1) {
+		__syncthreads();
+		conv_data_grad<SI, split_k(3 * SI * SI)>(params + off_w<N>(L), lds + lds_act<N>(L), lds + lds_act<N>(L - 1), split);
+		__syncthreads();
+		chain_backward<N, L - 1>(params, g, lds, split);
+	}
+}
+
+// One pair's step, its patches already in LDS behind a barrier: forward, Normalize2 / StereoJoin1 / Margin2 and their
+// backward passes, backward; the gradients go to g (the pair's slab row), the loss to *loss.
+template <class N>
+__device__ __forceinline__ void pair_step(const float *__restrict__ params, float margin, int pow, float inv_pairs, float *lds,
+                                          float *__restrict__ g, float *__restrict__ loss)
+{
+	static_assert(N::FM == FM && N::NP == 3 && 3 * N::PS * N::PS <= NT, "this family's feature maps; one thread per pixel of the pair's patches");
+	float *split = lds + lds_act<N>(N::NL + 1);
+	chain_forward<N>(params, lds, split);
+	if (threadIdx.x < 64) {
+		const float l = hinge_tail(lds + lds_act<N>(N::NL), threadIdx.x, margin, pow, inv_pairs);
+		if (threadIdx.x == 0) *loss = l;
+	}
+	__syncthreads();
+	chain_backward<N>(params, g, lds, split);
+}
+
+// The update: g = the slab's rows summed in pair order; v = mom * v - lr * g; w += v.  Block 0 also writes the mean loss.
+__device__ __forceinline__ void slab_sgd(const float *__restrict__ slab, const float *__restrict__ pair_losses, int n_pairs, int n_params,
+                                         float *__restrict__ params, float *__restrict__ moms, float lr, float mom, float *__restrict__ loss_out)
+{
+	const int j = blockIdx.x * blockDim.x + threadIdx.x;
+	if (j < n_params) {
+		float g = 0.f;
+		for (int p = 0; p < n_pairs; ++p) g += slab[(int64_t)p * n_params + j];
+		const float v = moms[j] * mom - lr * g;
+		moms[j] = v;
+		params[j] = params[j] + v;
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		float s = 0.f;
+		for (int p = 0; p < n_pairs; ++p) s += pair_losses[p];
+		*loss_out = s / (float)n_pairs;
+	}
+}
+
+// the workspace: a slab row and a loss per pair
+template <class N> static size_t step_workspace_bytes(int n_pairs)
+{
+	if (n_pairs < 1 || n_pairs > N::MAX_PAIRS) return 0;
+	return (size_t)n_pairs * (n_conv<N>() + 1) * sizeof(float);
+}
+
+template <class N>
+static int check_step_args(int n_pairs, const float *params, const float *moms, float margin, int pow, void *ws, size_t ws_bytes)
+{
+	MC_REQUIRE(n_pairs >= 1 && n_pairs <= N::MAX_PAIRS, "%s: n_pairs %d outside [1, %d]", N::PREFIX, n_pairs, N::MAX_PAIRS);
+	MC_REQUIRE(params && moms, "%s: null params / momenta", N::PREFIX);
+	MC_REQUIRE(pow == 1 || pow == 2, "%s: pow %d (Margin2 has pow 1 and 2, adcensus.cu:1427-1447)", N::PREFIX, pow);
+	MC_REQUIRE(isfinite(margin), "%s: margin not finite", N::PREFIX);
+	MC_REQUIRE(ws && ws_bytes >= step_workspace_bytes<N>(n_pairs), "%s: workspace of %zu bytes, %zu needed", N::PREFIX, ws_bytes,
+	           step_workspace_bytes<N>(n_pairs));
+	return 0;
 }
 
 }  // namespace mc

@@ -1,4 +1,4 @@
-// The range check of the four mc_train*_run entry points (train.hip, train_slow.hip, train_mb.hip, train_mb_slow.hip): do
+// The range check of the four mc_train*_run entry points, asked by the run driver they share (run_steps, train_net.h): do
 // the steps' rows [t0, t0 + n_steps * n_pairs) lie inside a permutation of n_perm rows?  Host code only, no HIP header, so
 // that tests/train_range_check.cpp can compile it alone under the sanitizers.
 #pragma once

@@ -1,9 +1,11 @@
 // The convolution GEMMs of the accurate architecture's training step on v_mfma_f32_16x16x4_f32 (fp32 in, fp32 accumulate;
 // 112 = 7 x 16 rows fill its tiles exactly), shared by train_slow.hip (four layers on 9 x 9 patches, a PAIR's three patches per
 // workgroup: NP = 3) and train_mb_slow.hip (five layers on 11 x 11 patches, ONE patch per workgroup: NP = 1).  112 feature
-// maps, every activation of the workgroup's NP patches in LDS as [NP][112][pixels], one workgroup of eight waves.
+// maps, every activation of the workgroup's NP patches in LDS as [NP][112][pixels], one workgroup of eight waves.  Then the
+// towers' layer chain over a net N of train_net.h, and where a patch's features sit in the FC stack's input.
 #pragma once
 #include "mc_common.h"
+#include "train_net.h"
 
 namespace mc {
 
@@ -132,6 +134,57 @@ __device__ void conv_data_grad(const float *__restrict__ w, const float *g, floa
 		*p = *p > 0.f ? v : 0.f;
 	};
 	block_gemm(N, mac, put);
+}
+
+// ---- the tower of a net N ------------------------------------------------------------------------------------------------
+template <class N> constexpr int TOWER_LDS_FLOATS = lds_act<N>(N::NL + 1);
+template <class N> constexpr size_t TOWER_LDS_BYTES = (size_t)TOWER_LDS_FLOATS<N> * sizeof(float);
+
+// the convolutions L .. NL of the workgroup's patches X into A_1 .. A_NL, all in LDS; a barrier after each
+template <class N, int L = 1>
+__device__ __forceinline__ void tower_forward(const float *__restrict__ params, float *lds)
+{
+	static_assert(N::FM == FM, "this family's feature maps");
+	conv_forward<N::NP, L == 1 ? 1 : FM, side<N>(L - 1)>(params + off_w<N>(L), params + off_b<N>(L), lds + lds_act<N>(L - 1), lds + lds_act<N>(L));
+	__syncthreads();
+	if constexpr (L < N::NL) tower_forward<N, L + 1>(params, lds);
+}
+
+// layers L .. 1 of the backward pass, A_L holding its gradient: layer l's weight and bias gradients into g (the workgroup's
+// slab row), then its data gradient over A_{l-1} in place; a barrier between any two GEMMs
+template <class N, int L = N::NL>
+__device__ __forceinline__ void tower_backward(const float *__restrict__ params, float *__restrict__ g, float *lds)
+{
+	constexpr int SI = side<N>(L - 1);
+	conv_weight_grad<N::NP, L == 1 ? 1 : FM, SI>(lds + lds_act<N>(L), lds + lds_act<N>(L - 1), g + off_w<N>(L), g + off_b<N>(L));
+	if constexpr (L > 1) {
+		__syncthreads();
+		conv_data_grad<N::NP, SI>(params + off_w<N>(L), lds + lds_act<N>(L), lds + lds_act<N>(L - 1));
+		__syncthreads();
+		tower_backward<N, L - 1>(params, g, lds);
+	}
+}
+
+// The FC stack's input a0 (2n, 2 * FM) has two rows per pair: [feat(left) | feat(positive)], [feat(left) | feat(negative)].
+// Feature c of patch (0 left, 1 positive, 2 negative) of a pair goes there ...
+__device__ __forceinline__ void scatter_feature(float *__restrict__ a0, int pair, int patch, int c, float v)
+{
+	float *r0 = a0 + (int64_t)(2 * pair) * (2 * FM), *r1 = r0 + 2 * FM;
+	if (patch == 0) {
+		r0[c] = v;
+		r1[c] = v;
+	} else if (patch == 1) {
+		r0[FM + c] = v;
+	} else {
+		r1[FM + c] = v;
+	}
+}
+
+// ... and its gradient comes back from dfeat, laid out as a0: the left patch gets the positive's, then the negative's sample
+__device__ __forceinline__ float gather_feature_grad(const float *__restrict__ dfeat, int pair, int patch, int c)
+{
+	const float *r0 = dfeat + (int64_t)(2 * pair) * (2 * FM), *r1 = r0 + 2 * FM;
+	return patch == 0 ? r0[c] + r1[c] : patch == 1 ? r0[FM + c] : r1[FM + c];
 }
 
 }  // namespace mc

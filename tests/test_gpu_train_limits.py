@@ -650,7 +650,7 @@ def refusal_buffers(tr):
 @pytest.mark.parametrize("fn,arg,value,names", REFUSALS, ids=["%s-%s-%s" % (c[0][9:], "+".join(c[1]) if isinstance(c[1], tuple) else c[1], c[2])
                                                               for c in REFUSALS])
 def test_refusals_are_loud_and_touch_nothing(tr, refusal_buffers, fn, arg, value, names):
-    """One case per MC_REQUIRE of train.hip and dataset.hip: MC_EINVAL, a message that names the argument, and no buffer
+    """One case per MC_REQUIRE that train.hip (with train_net.h and train_conv.h, which hold its shared checks) and dataset.hip can reach: MC_EINVAL, a message that names the argument, and no buffer
     written.  All of them are refused on the host before any launch."""
     import torch
     lib = tr.tl.load()

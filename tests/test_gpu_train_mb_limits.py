@@ -1,7 +1,7 @@
 """GPU: libmctrainmb.so (include/mc_train_mb.h) at its edges, as tests/test_gpu_train_limits.py has libmctrain.so: small and
 the largest batch sizes, the order in which the pairs' gradients are summed, `run` against the chain sample -> step_batch on
 the ragged store at plane borders (a 4 x 4 plane and plane ids outside the table among them) with the offset at its last
-legal value, and one refusal per MC_REQUIRE of train_mb.hip.
+legal value, and one refusal per MC_REQUIRE that train_mb.hip can reach.
 
 Every workspace is tests/test_gpu_train_slow_limits.py's `Guarded`: a 16-byte aligned slice of exactly
 `mc_train_mb_workspace_bytes(n)` bytes of NaN with 4096 sentinel words on either side.  The workspace is one gradient row
@@ -300,8 +300,9 @@ def call_with(lib, fn, tensors, scalars, arg=(), value=()):
 
 @pytest.mark.parametrize("fn,arg,value,names", REFUSALS, ids=["%s-%s-%s" % (c[0][12:], c[1], c[2]) for c in REFUSALS])
 def test_refusals_are_loud_and_touch_nothing(tm, refusal_buffers, fn, arg, value, names):
-    """One case per MC_REQUIRE of train_mb.hip, mc_train_mb_sample's included: MC_EINVAL, a message that names the argument,
-    and no buffer written.  All of them are refused on the host before any launch."""
+    """One case per MC_REQUIRE that train_mb.hip can reach (its shared checks are train_net.h's and train_conv.h's),
+    mc_train_mb_sample's included: MC_EINVAL, a message that names the argument, and no buffer written.  All of them are
+    refused on the host before any launch."""
     import torch
     lib = tm.tml.load()
     tensors, scalars, g = refusal_buffers

@@ -175,7 +175,7 @@ def reference(L, n_pairs):
 
 
 def areas(L, n_pairs):
-    """The libraries' workspace (carve in train_slow.hip / train_mb_slow.hip) restated: (name, first float, floats) of every
+    """The libraries' workspace (carve in train_slow_fc.h) restated: (name, first float, floats) of every
     area, each rounded up to 64 floats, and the total."""
     R, NIN, NH = 2 * n_pairs, 224, 384
     sizes = [("xs", n_pairs * 3 * L.PS * L.PS), ("a0", R * NIN)] + [("a%d" % l, R * NH) for l in range(1, L.L2 + 1)] + \
@@ -481,7 +481,7 @@ def call_with(L, fn, tensors, scalars, arg=(), value=()):
 @pytest.mark.parametrize("name,fn,arg,value,names", REFUSALS, ids=["%s-%s-%s-%s" % (c[0], c[1], "+".join(c[2]) if isinstance(c[2], tuple) else c[2], c[3])
                                                                    for c in REFUSALS])
 def test_refusals_are_loud_and_touch_nothing(name, fn, arg, value, names):
-    """One case per MC_REQUIRE of train_slow.hip and train_mb_slow.hip: MC_EINVAL, a message that names the argument, and no
+    """One case per MC_REQUIRE that train_slow.hip and train_mb_slow.hip can reach (their shared checks are train_net.h's and train_slow_fc.h's): MC_EINVAL, a message that names the argument, and no
     buffer written.  All of them are refused on the host before any launch."""
     import torch
     L = lib_of(name)

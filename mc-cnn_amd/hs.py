@@ -1,7 +1,7 @@
 """The reference's `hs.py ... test_te` search of the stereo method's parameters, on a test set resident on the device.
 
     python -m mc_cnn_amd.hs {random|hillclimb_slow|hillclimb_fast|hillclimb_dim} {kitti|kitti2015|mb} {fast|slow|ad|census} test_te
-           NET_FNAME [-n N] [-seed S] [-log FILE] [-data_dir D] [-disp_max D] [-cache_gb G] [-in_flight K] [-gpu g] [-no_reuse]
+           NET_FNAME [-n N] [-seed S] [-log FILE] [-data_dir D] [-disp_max D] [-cache_gb G] [-in_flight K] [-gpu g] [-no_reuse] [-l1 N]
 
 hs.py starts a fresh `main.lua` per candidate; here a candidate is `EvalSet.score` (evalset.py): the cost stage of every test
 pair stays on the device, and a candidate costs the post-CNN pipeline plus an error count per pair and one read-back.
@@ -17,8 +17,10 @@ dimension so (hillclimb_fast).  With no result yet a hill climb starts from the 
 One line per candidate, `score dataset arch action -name value ... -net_fname NET`, goes to stdout and, appended and flushed, to
 -log; hs.py's log files and these are interchangeable.  -n 0 (the default) runs until interrupted, as hs.py does.
 
-Not covered: the `train_tr` and `da` searches (the trainers' nets and augmentation grids are fixed shapes here), rgs*.py, and an
-on-disk volume cache (-make_cache / -use_cache).
+-l1 N names the depth of a fast NET_FNAME that `main.py ... -l1 N` trained (1..5); without it the net has the data set's.
+
+Not covered: the `train_tr` and `da` searches (of the train_tr grid's axes the depth is trainable here, the feature maps are not:
+fm 64 only), rgs*.py, and an on-disk volume cache (-make_cache / -use_cache).
 """
 import argparse
 import glob
@@ -56,8 +58,8 @@ for _a in ARCHS:
 
 def grid_of(dataset, arch, action="test_te"):
     if action != "test_te":
-        raise SystemExit("hs: the %s search is not supported: only test_te is (the trainers' nets and augmentation grids are fixed "
-                         "shapes here)" % action)
+        raise SystemExit("hs: the %s search is not supported: only test_te is (of the reference's train_tr grid the depth is "
+                         "trainable here, main.py -l1 1..5, but not the feature maps, fm 64 only; the da search is not built)" % action)
     return GRIDS[(dataset, arch)]
 
 
@@ -162,15 +164,17 @@ def search(method, evalset, grid, n, rng, results, emit=None, **score_args):
 
 
 # ---- the command line -------------------------------------------------------------------------------------------------------------
-def check_net(net_fname, dataset, arch):
-    """([(w, b)], fc layers or None) of NET_FNAME for a learned arch; SystemExit where the file does not fit the arch."""
+def check_net(net_fname, dataset, arch, l1=None):
+    """([(w, b)], fc layers or None) of NET_FNAME for a learned arch; SystemExit where the file does not fit the arch.  l1: the
+    -l1 of a fast net trained at another depth than the data set's."""
     from .main import FC_SHAPES, load_fc, load_net
     from .params import NET_SHAPES
     if arch not in ("fast", "slow"):
         return [], None
-    l1, fm = NET_SHAPES[(dataset, arch)]
+    default_l1, fm = NET_SHAPES[(dataset, arch)]
+    l1 = default_l1 if l1 is None else l1
     try:
-        layers = load_net(net_fname, dataset, arch)
+        layers = load_net(net_fname, dataset, arch, l1=l1)
         fc = load_fc(net_fname, dataset) if arch == "slow" else None
     except (KeyError, ValueError, OSError) as e:
         raise SystemExit("hs: %s does not fit %s %s: %s" % (net_fname, dataset, arch, e))
@@ -204,7 +208,11 @@ def parse(argv):
     ap.add_argument("-in_flight", type=int, default=2, help="streams the examples of a candidate are dealt over")
     ap.add_argument("-gpu", type=int, default=1, help="1-based, as main.py's")
     ap.add_argument("-no_reuse", action="store_true", help="run the whole pipeline for every candidate (no blur-only reuse)")
+    ap.add_argument("-l1", type=int, default=None, help="arch fast: the convolutions of NET_FNAME, 1..5, where not the data set's")
     opt = ap.parse_args(argv)
+    if opt.l1 is not None and (opt.arch != "fast" or not 1 <= opt.l1 <= 5):
+        raise SystemExit("hs: -l1 %d for arch %s: -l1 1..5 names the depth of a fast net (main.py -l1); the other archs keep "
+                         "their data set's" % (opt.l1, opt.arch))
     if opt.action != "test_te":
         grid_of(opt.dataset, opt.arch, opt.action)   # refuses
     if opt.n < 0 or opt.in_flight < 1 or opt.cache_gb < 0:
@@ -216,7 +224,7 @@ def parse(argv):
 def main(argv=None):
     opt = parse(list(sys.argv[1:] if argv is None else argv))
     grid = grid_of(opt.dataset, opt.arch, opt.action)
-    layers, fc_layers = check_net(opt.net_fname, opt.dataset, opt.arch)
+    layers, fc_layers = check_net(opt.net_fname, opt.dataset, opt.arch, opt.l1)
     import torch
     from .evalset import EvalSet
     dev = torch.device("cuda", opt.gpu - 1)

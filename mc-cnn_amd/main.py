@@ -17,6 +17,12 @@ w1,b1,...,w<l1>,b<l1> (w_i: (fm, in, 3, 3); arch slow also fw1,fb1,...), or `ran
 (`-a train_tr` trains one: see below).  Hyper-parameter flags (-L1 -tau1 -cbca_i1 -cbca_i2 -pi1 -pi2 -sgm_i
 -sgm_q1 -sgm_q2 -alpha1 -tau_so -blur_sigma -blur_t) default to main.lua's per-(dataset, arch) tables.
 
+Arch fast takes main.lua's net flags: -l1 (3x3 convolutions, 1..5; default NET_SHAPES: 4 on kitti / kitti2015, 5 on mb), -fm
+(64 only) and -ks (3 only).  -l1 sizes a `random:` or `.npz` net (a `.t7` carries its own depth) and, where it is not the
+default, sends -a train_tr | train_all through train_depth.py (libmctraindepth.so: the same step at any depth, on either image
+store); `route` is where that is decided.  -L1 is another flag, the cross arm length.  The three flags are refused on slow, ad
+and census.
+
 `-a train_tr | train_all` (kitti | kitti2015; main.lua:602-890) train the net on the GPU from `-data_dir` (arch fast:
 train.py, libmctrain.so; arch slow: train_slow.py, libmctrainslow.so, with train_slow.parse's flags) and save
 net/net_<args>.t7; train_tr then runs test_te.  `training_module` is the one routing table of the four trainable nets, whose
@@ -37,7 +43,7 @@ import numpy as np
 
 from .binio import write_bin
 from .params import NET_SHAPES, TABLES
-from .train_common import new_parser, pipeline_prm
+from .train_common import add_net_flags, check_net_flags, new_parser, pipeline_prm, refuse_net_flags
 
 
 def rgb2y(img):
@@ -68,8 +74,11 @@ def parse(argv):
         raise SystemExit("usage: main.py {kitti|kitti2015|mb} {fast|slow|ad|census} -a {predict|time|train_tr|train_all|test_te|"
                          "test_all} [flags]  (main.lua:10-13)")
     dataset, arch = argv[0], argv[1]
+    refuse_net_flags(argv, "main.py")
     t = TABLES[(dataset, arch)]
     ap = new_parser(dataset, arch, t, FAST_TRAIN_DEFAULTS)
+    if arch == "fast":
+        add_net_flags(ap, dataset, arch)
     ap.add_argument("-a", default="predict", choices=["predict", "time"] + list(TRAIN_ACTIONS) + ["submit"])
     ap.add_argument("-left", default="")
     ap.add_argument("-right", default="")
@@ -80,6 +89,8 @@ def parse(argv):
         ap.add_argument("-at", type=int, default=0, choices=(0, 1),
                         help="1: train on KITTI 2012 and 2015 together (main.lua:72,208,236, 403-426)")
     opt = ap.parse_args(argv[2:])
+    if arch == "fast":
+        check_net_flags(opt, "main.py")
     if opt.a not in ("predict", "time") and (opt.a not in TRAIN_ACTIONS or dataset not in ("kitti", "kitti2015") or arch != "fast"):
         raise SystemExit("main.py: -a %s is not supported for %s %s; training and testing cover -a %s for "
                          "{kitti|kitti2015} fast only (arch slow trains through train_slow.parse, which main() routes "
@@ -114,10 +125,11 @@ def reference_nets(net_fname, arch):
     return _t7_cache[key]
 
 
-def load_net(net_fname, dataset, arch, n_input_plane=1):
+def load_net(net_fname, dataset, arch, n_input_plane=1, l1=None):
     """[(w, b)] of the feature net: from the reference's `.t7` (torch.save(..., 'ascii'), main.lua:587-600), an .npz, or
-    seeded random (`random:<seed>`)."""
-    l1, fm = NET_SHAPES[(dataset, arch)]
+    seeded random (`random:<seed>`).  l1: the -l1 of a fast net where it is not the data set's (a `.t7` carries its own)."""
+    default_l1, fm = NET_SHAPES[(dataset, arch)]
+    l1 = default_l1 if l1 is None else l1
     if net_fname.endswith(".t7"):
         layers = reference_nets(net_fname, arch)[0]
         if not layers:
@@ -213,10 +225,24 @@ def training_module(argv):
     return mod if mod is not None and argv[argv.index("-a", 2) + 1] in mod.ACTIONS else None
 
 
-def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
+def route(argv):
+    """(mod, trainer, dataset, arch, opt, prm) of a command line: mod is `training_module(argv)`, whose `parse` gave the rest
+    (None: `parse` above did); trainer is the module whose `train` runs -a train_tr | train_all: train_depth for arch fast with
+    a -l1 other than the data set's (libmctraindepth.so), otherwise mod, or train where mod is None."""
     mod = training_module(argv)
     dataset, arch, opt, prm = parse(argv) if mod is None else mod.parse(argv)
+    trainer = mod
+    if arch == "fast" and opt.a in TRAIN_ACTIONS:
+        if opt.l1 != NET_SHAPES[(dataset, arch)][0]:
+            from . import train_depth as trainer
+        elif mod is None:
+            from . import train as trainer
+    return mod, trainer, dataset, arch, opt, prm
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    mod, trainer, dataset, arch, opt, prm = route(argv)
     import torch
     from .predict import Workspace, stereo_predict_fused
     if arch not in ("fast", "slow", "ad", "census"):
@@ -224,7 +250,8 @@ def main(argv=None):
     dev = torch.device("cuda", opt.gpu - 1)
     torch.cuda.set_device(dev)
     learned = arch in ("fast", "slow")
-    layers = device_layers(load_net(opt.net_fname, dataset, arch), dev) if learned else []   # resident: uploaded once
+    l1 = getattr(opt, "l1", None)         # arch fast: the depth of a random: or .npz net
+    layers = device_layers(load_net(opt.net_fname, dataset, arch, l1=l1), dev) if learned else []   # resident: uploaded once
     fc_layers = load_fc(opt.net_fname, dataset) if arch == "slow" else None
     prm["border_n"] = len(layers)  # (1 + l1*(3-1) - 1) / 2, main.lua:382-391,923
 
@@ -249,8 +276,8 @@ def main(argv=None):
         if mod is None:
             from . import train as mod
         if opt.a in ("train_tr", "train_all"):   # main.lua:602-890; each train() keeps its own leading arguments
-            lead = () if dataset == "mb" else (dataset, arch) if arch == "fast" else (dataset,)
-            opt.net_fname = mod.train(*lead, opt, argv[2:], dev)
+            lead = () if trainer is mod and dataset == "mb" else (dataset, arch) if arch == "fast" else (dataset,)
+            opt.net_fname = trainer.train(*lead, opt, argv[2:], dev)
             if opt.a == "train_all":            # main.lua:884-887 goes on to submit, which is out of scope
                 return 0
             opt.a = "test_te"

@@ -18,7 +18,7 @@ import time
 
 import numpy as np
 
-from .params import SM_SKIP, SM_TERMINATE
+from .params import NET_SHAPES, SM_SKIP, SM_TERMINATE
 
 # ---- flags -------------------------------------------------------------------------------------------------------------
 PIPELINE_FLAGS = (("L1", "cbca_i1", "cbca_i2", "sgm_i"),                                                      # int
@@ -54,6 +54,42 @@ def new_parser(dataset, arch, t, train_defaults):
     ap.add_argument("-epochs", type=int, default=14, help="main.lua:777 runs 14")
     ap.add_argument("-max_steps", type=int, default=0, help="stop training after this many steps in all (0: no limit)")
     return ap
+
+
+NET_FLAGS = ("-l1", "-fm", "-ks")   # main.lua:212-214, 240-242, 271-273: what the reference builds the net from
+L1_TRAINABLE = (1, 5)               # include/mc_train_depth.h
+
+
+def add_net_flags(ap, dataset, arch):
+    """-l1 (3x3 convolutions; not -L1, the cross arm length: the flags are case-sensitive), -fm (feature maps) and -ks (kernel
+    size) with the defaults of (dataset, arch)."""
+    l1, fm = NET_SHAPES.get((dataset, arch), (0, 0))
+    ap.add_argument("-l1", type=int, default=l1, help="convolution layers of the fast net, %d..%d" % L1_TRAINABLE)
+    ap.add_argument("-fm", type=int, default=fm, help="feature maps per layer; only 64 is supported")
+    ap.add_argument("-ks", type=int, default=3, help="kernel size; only 3 is supported")
+
+
+def refuse_net_flags(argv, who):
+    """-l1 / -fm / -ks on a command line whose arch is not fast: arch slow has the shape its libraries are compiled for, ad and
+    census have no net."""
+    given = [a for a in argv[2:] if a in NET_FLAGS]
+    if given and len(argv) >= 2 and argv[1] != "fast":
+        why = ("its towers (fm 112) run on another GEMM family, compiled for the data set's l1" if argv[1] == "slow" else "it has no net")
+        raise SystemExit("%s: %s is not supported for arch %s: %s; -l1 %d..%d (with -fm 64 -ks 3) builds {kitti|kitti2015|mb} fast"
+                         % ((who, given[0], argv[1], why) + L1_TRAINABLE))
+
+
+def check_net_flags(opt, who):
+    """What of -l1 / -fm / -ks the fast net's kernels serve; names it where they do not."""
+    if not L1_TRAINABLE[0] <= opt.l1 <= L1_TRAINABLE[1]:
+        raise SystemExit("%s: -l1 %d is not supported: l1 %d..%d are (a pair's step keeps every activation in a CU's 160 KiB of LDS, "
+                         "which six layers on 13 x 13 patches exceed)" % ((who, opt.l1) + L1_TRAINABLE))
+    if opt.fm != 64:
+        raise SystemExit("%s: -fm %d is not supported: only -fm 64 is (the training GEMMs tile 64 output maps as two 32 x 32 tiles and "
+                         "the hinge gives each of a wave's 64 lanes a channel); -l1 %d..%d is" % ((who, opt.fm) + L1_TRAINABLE))
+    if opt.ks != 3:
+        raise SystemExit("%s: -ks %d is not supported: only -ks 3 is (every convolution kernel here is 3 x 3); -l1 %d..%d is"
+                         % ((who, opt.ks) + L1_TRAINABLE))
 
 
 def pipeline_prm(t, opt):

@@ -86,6 +86,7 @@ def parse(argv):
     if len(argv) < 2 or argv[0] not in ("kitti", "kitti2015") or argv[1] != "slow":
         raise SystemExit("train_slow: training and testing of arch slow cover {kitti|kitti2015} slow -a %s "
                          "(mb slow's l1 5 / l2 3 net trains through train_mb_slow.parse, mb fast through train_mb.parse; -a submit is out of scope)" % " | ".join(ACTIONS))
+    common.refuse_net_flags(argv, "train_slow")
     dataset = argv[0]
     t = TABLES[(dataset, "slow")]
     ap = common.new_parser(dataset, "slow", t, SLOW_TRAIN_DEFAULTS)

@@ -421,4 +421,22 @@ int mc_predict_timed(const mc_params *p, const float *x0, const float *x1, const
 	return rc;
 }
 
+// ---- for the tests only: not declared in include/mc_adcensus.h, not part of the ABI ----
+#pragma GCC visibility push(default)
+// the fast path's schedule: 1 / 2 force one lane / two lanes (2: also where the callers' streams alternate), 0 returns to MC_PREDICT_LANES,
+// -1 only asks; returns the one in force
+int mc_test_predict_lanes(int set) { return predict_lanes(set); }
+
+// stereo_join_hwd (StereoJoin + fix_border into mc_predict's (H,W,ds) layout) for the chosen volumes: sides bit 0 left, bit 1 right
+int mc_test_stereo_join_hwd(const float *featL, const float *featR, float *volL, float *volR, int C, int D, int ds, int H, int W, int border_n,
+                            int sides, void *stream)
+{
+	MC_REQUIRE(featL && featR && volL && volR, "mc_test_stereo_join_hwd: null pointer");
+	MC_REQUIRE(dims_ok(D, H, W) && C >= 1 && C <= MC_JOIN_MAX_C && ds >= D && border_n >= 0 && border_n < W, "mc_test_stereo_join_hwd: bad dims");
+	const int64_t HW = (int64_t)H * W;   // the kernels' 32-bit offsets, as mc_predict checks them in front of its fast path
+	MC_REQUIRE((int64_t)W * ds * 4 < ((int64_t)1 << 31) && ((int64_t)(C + 64) * HW + W) * 4 < ((int64_t)1 << 31), "mc_test_stereo_join_hwd: too large");
+	return stereo_join_hwd(featL, featR, volL, volR, C, D, ds, H, W, border_n, as_stream(stream), sides);
+}
+#pragma GCC visibility pop
+
 }  // extern "C"

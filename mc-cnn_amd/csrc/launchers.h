@@ -3,6 +3,7 @@
 #pragma once
 #include "cbca_common.h"
 
+#include <mutex>
 #include <vector>
 
 namespace mc {
@@ -26,7 +27,8 @@ int normalize_forward(const float *in, float *norm, float *out, int N, int C, in
 
 // stereo_join.hip
 int stereo_join_dhw(const float *fL, const float *fR, float *volL, float *volR, int C, int D, int H, int W, hipStream_t st);
-int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, int C, int D, int ds, int H, int W, int n, hipStream_t st);
+int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, int C, int D, int ds, int H, int W, int n, hipStream_t st,
+                    int sides = 3);   // bit 0: the left volume, bit 1: the right one
 int ad_tiled(const float *x0, const float *x1, float *vol, int D, int H, int W, int direction, hipStream_t st);
 size_t census_scratch_bytes(int Cimg, int H, int W);
 int census_sig(const float *x0, const float *x1, float *vol, void *scratch, int Cimg, int D, int H, int W, int direction, hipStream_t st);
@@ -91,6 +93,15 @@ struct Plan {
 	void *cplan[2];             // null where the direction has none
 };
 Plan make_plan(const mc_params *p, int D, int H, int W, void *base = nullptr);
+
+// the fast path's two lanes: MC_PREDICT_LANES (1 or 2, default 2), and what a caller's stream keeps for its right lane
+int parse_predict_lanes(const char *s);
+int predict_lanes(int set = -1, bool *is_forced = nullptr);   // set 1 / 2: force that schedule (the tests), 0: back to the environment's; returns the one in force
+struct Lanes {
+	hipStream_t side = nullptr;
+	hipEvent_t fork = nullptr, join_left = nullptr, right_done = nullptr;
+	std::mutex mu;
+};
 
 struct StageTimer {   // mc_predict_timed: an event at every stage boundary
 	bool on = false;

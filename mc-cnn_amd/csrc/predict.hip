@@ -2,6 +2,7 @@
 // -sm_terminate / -sm_skip leave, and the launches in order.  The extern "C" surface is api.hip.
 #include "launchers.h"
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -48,6 +49,96 @@ static int gaussian_cached(double sigma, const float *&out)
 	out = cache[{dev, sigma}] = dk;
 	return 0;
 }
+
+// ---- the fast path's two lanes (predict_impl) ----
+// MC_PREDICT_LANES, read once per process: "1" keeps the fast path on the caller's stream alone, anything else (and no value) is the
+// default, 2.  A handle for A/B measurements and for the tests, which get both schedules from one library through predict_lanes(1 / 2).
+int parse_predict_lanes(const char *s) { return (s && s[0] == '1' && s[1] == '\0') ? 1 : 2; }
+int predict_lanes(int set, bool *is_forced)
+{
+	static const int from_env = parse_predict_lanes(getenv("MC_PREDICT_LANES"));
+	static std::atomic<int> forced{0};   // 0: what the environment says
+	if (set >= 0 && set <= 2) forced.store(set);
+	const int f = forced.load();
+	if (is_forced) *is_forced = f != 0;
+	return f ? f : from_env;
+}
+
+#define MC_HIP(call, what) do { const hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("mc_predict: %s: %s", what, hipGetErrorString(e_)); return (int)e_; } } while (0)
+
+// The side stream (non-blocking) and the three events of a caller's stream, made at the first two-lane call on (device, stream) and kept,
+// like the Gaussian table: nothing is created per call.  `mu` is held while a call enqueues between its fork and its join: two host
+// threads on ONE caller stream would otherwise re-record an event between the other's record and wait.
+// Several caller streams in one process (pairs in flight): their pairs already run beside each other, and with a side stream each -- or
+// with one left over from a single-stream phase: the process then has more streams than the four hardware queues it opens, and two
+// callers share one -- K = 2 and 3 got slower (profiles/two_lane_ab.txt).  So once a device has seen a fast-path call from a second caller
+// stream, it keeps one lane for the life of the process: no side stream is made any more (out = null), and those that exist and are not
+// between a fork and a join are released.  A rule on the order of the calls alone: nothing is asked of the device.  `solo_only` = false
+// (the tests' forced setting) stands outside the rule.  The entry comes back locked (`held`), taken under the cache's own lock, so that
+// no entry is released while a call holds or awaits it.
+static int lanes_cached(hipStream_t st, bool solo_only, Lanes *&out, std::unique_lock<std::mutex> &held)
+{
+	static std::mutex mu;
+	static auto &cache = *new std::map<std::pair<int, hipStream_t>, Lanes *>;   // never destroyed: a call may be under way at exit
+	static auto &first_caller = *new std::map<int, hipStream_t>;               // per device: the caller stream of its first fast-path call
+	static auto &many_callers = *new std::map<int, bool>;
+	int dev = 0;
+	MC_HIP(hipGetDevice(&dev), "hipGetDevice");
+	std::lock_guard<std::mutex> lk(mu);
+	out = nullptr;
+	if (solo_only) {
+		auto fc = first_caller.find(dev);
+		if (fc == first_caller.end()) first_caller[dev] = st;
+		else if (fc->second != st) many_callers[dev] = true;
+		if (many_callers[dev]) {
+			for (auto it = cache.begin(); it != cache.end();) {
+				Lanes *l = it->second;
+				if (it->first.first != dev || !l->mu.try_lock()) { ++it; continue; }
+				(void)hipStreamDestroy(l->side);   // (what it still has queued runs to its end: the caller's stream waits for it)
+				for (hipEvent_t ev : {l->fork, l->join_left, l->right_done}) (void)hipEventDestroy(ev);
+				l->mu.unlock();
+				delete l;
+				it = cache.erase(it);
+			}
+			return 0;
+		}
+	}
+	auto it = cache.find({dev, st});
+	if (it == cache.end()) {
+		Lanes *l = new Lanes;
+		hipError_t e = hipStreamCreateWithFlags(&l->side, hipStreamNonBlocking);
+		hipEvent_t *const evs[3] = {&l->fork, &l->join_left, &l->right_done};
+		for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(evs[i], hipEventDisableTiming);
+		if (e != hipSuccess) {
+			set_error("mc_predict: side stream and events: %s", hipGetErrorString(e));
+			for (hipEvent_t *ev : evs) if (*ev) (void)hipEventDestroy(*ev);
+			if (l->side) (void)hipStreamDestroy(l->side);
+			delete l;
+			return (int)e;
+		}
+		it = cache.emplace(std::make_pair(dev, st), l).first;
+	}
+	out = it->second;
+	held = std::unique_lock<std::mutex>(out->mu);
+	return 0;
+}
+
+// From the fork on, whichever way predict_impl returns, the caller's stream waits for the side stream's last recorded event: it is
+// never left ahead of work that still writes the workspace.  (Declared after the lock on Lanes::mu: the wait is enqueued under it.)
+struct LaneJoin {
+	hipStream_t st = nullptr;
+	Lanes *ln = nullptr;
+	bool armed = false;
+	int join()   // side: record right_done; caller's stream: wait for it
+	{
+		if (!armed) return 0;
+		armed = false;
+		MC_HIP(hipEventRecord(ln->right_done, ln->side), "hipEventRecord (right lane done)");
+		MC_HIP(hipStreamWaitEvent(st, ln->right_done, 0), "hipStreamWaitEvent (right lane done)");
+		return 0;
+	}
+	~LaneJoin() { (void)join(); }
+};
 
 // -sm_terminate / -sm_skip (main.lua:956,988-1040) are identical for both directions, so for the three volume stages they
 // reduce to effective iteration counts
@@ -228,16 +319,69 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	const bool join_fits = (int64_t)W * ((D + 3) / 4 * 4) * 4 < ((int64_t)1 << 31) && ((int64_t)(C + 64) * HW + W) * 4 < ((int64_t)1 << 31);
 	// the volumes hold NaN wherever the partner pixel lies outside the image (left: d > x, right: x + d >= W), sgm_sweeps' `tri`
 	bool nan_triangle = false;
+	// (B) below, for volumes [v0, v0 + nv) on stream s
+	float *dispv[2] = {pl.img[0], pl.img[1]};  // [0] = left disparity (disp[2] in Lua), [1] = right
+	bool have_disp = false;
+	auto sgm_iterations = [&](int v0, int nv, hipStream_t s) -> int {
+		for (int it = 0; it < n_sgm; ++it) {
+			// out:zero(); sgm2(...); vol:copy(out):div(4)  (main.lua:1013-1018): the zero is folded
+			// into the first sweep (0 + L_0) and the /4 into the last
+			const float *Cv[2];
+			float *outv[2], *scratch[2], *dv[2];
+			int dir[2];
+			for (int k = 0; k < nv; ++k) {
+				Cv[k] = cur[v0 + k]; outv[k] = other(v0 + k); scratch[k] = pl.bufC[v0 + k]; dv[k] = dispv[v0 + k]; dir[k] = direction[v0 + k];
+			}
+			const bool am = (it == n_sgm - 1) && n_cbca2 == 0;
+			// the right volume's final costs: where no CBCA-2 follows, only right.bin reads them (sub-pixel refinement reads the
+			// left volume, the LR check the arg-min maps that the up sweep writes regardless) -- not stored unless asked for.
+			// sgm_sweeps counts its bits from the first volume it is given: bit 1 of a pair, bit 0 of the right volume alone
+			const bool has_right = v0 + nv == 2;
+			const unsigned drop_final = (am && has_right && !volR_out) ? 1u << (1 - v0) : 0u;
+			const int rc1 = sgm_sweeps(Cv, outv, scratch, am ? dv : nullptr, dir, nv, H, W, D, ds, pl.maps, p->pi1, p->pi2, p->alpha1,
+			                           p->sgm_q1, p->sgm_q2, true, drop_final, nan_triangle, s);
+			if (rc1) return rc1;
+			have_disp = am;
+			for (int k = 0; k < nv; ++k) cur[v0 + k] = outv[k];
+		}
+		return 0;
+	};
+	// Two lanes: the left volume's chain stays on the caller's stream, the right volume's runs on a side stream one stage behind it --
+	// its StereoJoin (matrix pipes) beside the left volume's horizontal sweeps (memory), then sweep beside sweep -- and joins in front of
+	// the LR check.  The volumes share nothing between StereoJoin and the LR check but the SGM maps, which both only read.
+	std::unique_lock<std::mutex> lane_lock;
+	LaneJoin lane_b;
 	if (from_feat && n_cbca1 == 0 && n_sgm > 0 && join_fits) {
 		// fast path: StereoJoin straight into (H,W,ds) with NaN fill and fix_border folded in
-		RUN(stereo_join_hwd(featL, featR, pl.bufA[0], pl.bufA[1], C, D, ds, H, W, p->border_n, st));
+		bool forced = false;
+		const bool two_lanes = nvol == 2 && n_cbca2 == 0 && C <= 64 && !tm.on && predict_lanes(-1, &forced) == 2;
 		cur[0] = pl.bufA[0]; cur[1] = pl.bufA[1];
 		hwd = true;
+		nan_triangle = true;   // (why: below)
+		Lanes *ln = nullptr;
+		if (two_lanes) RUN(lanes_cached(st, !forced, ln, lane_lock));
+		if (ln) {
+			MC_HIP(hipEventRecord(ln->fork, st), "hipEventRecord (fork)");   // after sgm_prep: the maps are the right lane's too
+			RUN(stereo_join_hwd(featL, featR, pl.bufA[0], pl.bufA[1], C, D, ds, H, W, p->border_n, st, 1));
+			MC_HIP(hipEventRecord(ln->join_left, st), "hipEventRecord (left join)");
+			// the right lane, start to end; the stagger: its join starts when the left one has finished, not beside it
+			lane_b.st = st; lane_b.ln = ln; lane_b.armed = true;
+			MC_HIP(hipStreamWaitEvent(ln->side, ln->fork, 0), "hipStreamWaitEvent (fork)");
+#ifndef MC_LANES_NO_STAGGER
+			MC_HIP(hipStreamWaitEvent(ln->side, ln->join_left, 0), "hipStreamWaitEvent (left join)");
+#endif
+			RUN(stereo_join_hwd(featL, featR, pl.bufA[0], pl.bufA[1], C, D, ds, H, W, p->border_n, ln->side, 2));
+			RUN(sgm_iterations(1, 1, ln->side));
+			if (volR_out) RUN(transpose(cur[1], volR_out, HW, D, ds, HW, 1.0f, ln->side));
+			if (dispR0_out) RUN(scale(dispv[1], dispR0_out, HW, 1.0f, ln->side));
+			// (right_done is recorded behind these launches where the lanes meet, or on the way out of a failed call: LaneJoin)
+		} else {
+			RUN(stereo_join_hwd(featL, featR, pl.bufA[0], pl.bufA[1], C, D, ds, H, W, p->border_n, st));
+		}
 		// stereo_join_hwd writes NaN there itself.  Its fix_border_hwd then copies the whole cost vector of column W - (n + 1) to the
 		// columns right of it (left volume) and of column n to the columns left of it (right volume): the source column has no more
 		// live disparities than any target (x + 1 grows to the right, W - x to the left), so the copy may add NaNs below a
 		// target's Dv but leaves none out at or above it.  Every SGM iteration keeps the triangle NaN (NaN + anything).
-		nan_triangle = true;
 		tm.mark(MC_STAGE_JOIN);
 	} else {
 		if (from_feat) {  // main.lua:946-949
@@ -257,8 +401,7 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	}
 
 	// ---- (B) SGM, main.lua:1007-1030 ----
-	float *dispv[2] = {pl.img[0], pl.img[1]};  // [0] = left disparity (disp[2] in Lua), [1] = right
-	bool have_disp = false;
+	const int nmain = lane_b.armed ? 1 : nvol;   // volumes whose chain runs on the caller's stream
 	if (n_sgm > 0) {
 		if (!hwd) {  // vol:transpose(2,3):transpose(3,4):clone(), main.lua:1008
 			for (int v = 0; v < nvol; ++v) {
@@ -269,20 +412,7 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 			hwd = true;
 			tm.mark(MC_STAGE_LAYOUT);
 		}
-		for (int it = 0; it < n_sgm; ++it) {
-			// out:zero(); sgm2(...); vol:copy(out):div(4)  (main.lua:1013-1018): the zero is folded
-			// into the first sweep (0 + L_0) and the /4 into the last
-			const float *Cv[2] = {cur[0], cur[1]};
-			float *outv[2] = {other(0), other(1)};
-			const bool am = (it == n_sgm - 1) && n_cbca2 == 0;
-			// the right volume's final costs: where no CBCA-2 follows, only right.bin reads them (sub-pixel refinement reads the
-			// left volume, the LR check the arg-min maps that the up sweep writes regardless) -- not stored unless asked for
-			const unsigned drop_final = (am && nvol == 2 && !volR_out) ? 2u : 0u;
-			RUN(sgm_sweeps(Cv, outv, pl.bufC, am ? dispv : nullptr, direction, nvol, H, W, D, ds, pl.maps, p->pi1, p->pi2, p->alpha1,
-			               p->sgm_q1, p->sgm_q2, true, drop_final, nan_triangle, st));
-			have_disp = am;
-			cur[0] = outv[0]; cur[1] = outv[1];
-		}
+		RUN(sgm_iterations(0, nmain, st));
 		tm.mark(MC_STAGE_SGM);
 		if (n_cbca2 > 0) {  // back to (D,H,W): vol:copy(out:transpose(3,4):transpose(2,3)), main.lua:1019-1020
 			for (int v = 0; v < nvol; ++v) {
@@ -307,14 +437,17 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	}
 	// ---- left.bin / right.bin contents, main.lua:1042-1047 ----
 	float *vout[2] = {volL_out, volR_out};
-	for (int v = 0; v < nvol; ++v) {
+	for (int v = 0; v < nmain; ++v) {   // (the right lane has exported its own)
 		if (!vout[v]) continue;
 		if (hwd) RUN(transpose(cur[v], vout[v], HW, D, ds, HW, 1.0f, st));
 		else RUN(scale(cur[v], vout[v], V, 1.0f, st));
 	}
 	if (dispL0_out) RUN(scale(dispv[0], dispL0_out, HW, 1.0f, st));
-	if (dispR0_out) RUN(scale(dispv[1], dispR0_out, HW, 1.0f, st));
+	if (dispR0_out && nmain == nvol) RUN(scale(dispv[1], dispR0_out, HW, 1.0f, st));
 	tm.mark(MC_STAGE_ARGMIN);
+	// the lanes meet: everything below is the caller's stream alone (the LR check reads the right arg-min)
+	RUN(lane_b.join());
+	if (lane_lock.owns_lock()) lane_lock.unlock();
 
 	// ---- (C) post-processing on the LEFT disparity, main.lua:1054-1081 ----
 	// every stage reads `d` and writes the next free image; -sm_skip / -sm_terminate drop stages (main.lua:1057-1079)
@@ -364,6 +497,7 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	}
 	tm.mark(MC_STAGE_POST);
 #undef RUN
+#undef MC_HIP
 	return 0;
 }
 

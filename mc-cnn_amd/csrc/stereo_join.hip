@@ -373,33 +373,37 @@ __device__ __forceinline__ void join_owner_tiles(const float *__restrict__ fL, c
 template <int KSTEPS, int NT = MC_JOIN_NT>
 __global__ void __launch_bounds__(64 * MC_JOIN_WPB) join_owner_kernel(const float *__restrict__ fL, const float *__restrict__ fR,
                                                          float *__restrict__ volL, float *__restrict__ volR, int C, int D, int ds,
-                                                         int H, int W, int pairs_per_row)
+                                                         int H, int W, int pairs_per_row, int sides)
 {
 	__shared__ __attribute__((aligned(16))) float rings[MC_JOIN_WPB][NT * 32 * 64];
 	const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	// XCD-aware mapping as in join_mfma_kernel: all blocks of one image row on one XCD
 	const int b = blockIdx.x;
 	const int xcd = b & 7, k = b >> 3;
-	const int blocks_per_row = (2 * pairs_per_row + MC_JOIN_WPB - 1) / MC_JOIN_WPB;
+	// sides (bit 0 left volume, bit 1 right): the grid holds the chosen side's waves only; waves [0, pairs_per_row) of a row are
+	// the left volume's, the rest the right one's, and a launch for the right volume alone starts at the second half
+	const int row_waves = sides == 3 ? 2 * pairs_per_row : pairs_per_row;
+	const int blocks_per_row = (row_waves + MC_JOIN_WPB - 1) / MC_JOIN_WPB;
 	const int y = (k / blocks_per_row) * 8 + xcd;
-	const int w = (k % blocks_per_row) * MC_JOIN_WPB + wid;
-	if (y >= H || w >= 2 * pairs_per_row) return;
+	const int w0 = (k % blocks_per_row) * MC_JOIN_WPB + wid;
+	if (y >= H || w0 >= row_waves) return;
+	const int w = sides == 2 ? w0 + pairs_per_row : w0;
 	if (w < pairs_per_row) join_owner_tiles<KSTEPS, 0, NT>(fL, fR, volL, C, D, ds, H, W, y, NT * w, rings[wid]);
 	else join_owner_tiles<KSTEPS, 1, NT>(fL, fR, volR, C, D, ds, H, W, y, NT * (w - pairs_per_row), rings[wid]);
 }
 
 // fix_border (main.lua:922-927) on (H,W,ds): the n outermost pixels of one side replicate the
 // (n+1)-th pixel's whole cost vector.  One wave per (volume, row, border pixel): the left volume's right border (direction -1),
-// then the right volume's left border (direction +1).
+// then the right volume's left border (direction +1); sides (bit 0 left, bit 1 right) as in join_owner_kernel.
 __global__ void __launch_bounds__(256) fix_border_hwd_kernel(float *__restrict__ volL, float *__restrict__ volR, int D, int ds, int H,
-                                                             int W, int n)
+                                                             int W, int n, int sides)
 {
 	const int lane = threadIdx.x & 63;
 	int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
 	const int64_t per = (int64_t)H * n;
-	if (w >= 2 * per) return;
-	const bool right = w >= per;
-	if (right) w -= per;
+	if (w >= (sides == 3 ? 2 * per : per)) return;
+	const bool right = sides == 2 || w >= per;
+	if (w >= per) w -= per;
 	float *vol = right ? volR : volL;
 	const int y = (int)(w / n), i = (int)(w % n) + 1;
 	const int dst = right ? i - 1 : W - i;
@@ -409,8 +413,10 @@ __global__ void __launch_bounds__(256) fix_border_hwd_kernel(float *__restrict__
 	for (int d = lane; d < D; d += 64) t[d] = s[d];
 }
 
+// sides: bit 0 the left volume, bit 1 the right one -- both kernels then run the chosen volume's waves only (the owner kernel; the
+// wide-C kernel computes both volumes from one product and takes no selector)
 int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, int C, int D, int ds, int H, int W, int n,
-                    hipStream_t st)
+                    hipStream_t st, int sides)
 {
 	const int rows8 = (H + 7) / 8;
 	const int ks = (C + 1) / 2;
@@ -418,13 +424,15 @@ int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, 
 	// mc_predict's (H,W,Dp) workspace volumes only: the owner kernel's 16-byte runs need them
 	MC_REQUIRE(ds % 4 == 0 && (uintptr_t)volL % 16 == 0 && (uintptr_t)volR % 16 == 0,
 	           "stereo_join_hwd: the volumes must be 16-byte aligned with a pixel stride ds %% 4 == 0 (ds = %d)", ds);
+	MC_REQUIRE(sides >= 1 && sides <= 3 && (sides == 3 || ks <= 32), "stereo_join_hwd: sides=%d (C = %d)", sides, C);
+	const int nside = sides == 3 ? 2 : 1;
 	const char *what = "stereo_join_hwd";
 	if (ks <= 32) {
 		const int tiles_own = ((W + 31) / 32 + MC_JOIN_NT - 1) / MC_JOIN_NT;   // groups of MC_JOIN_NT 32-pixel tiles per image row and volume
-		const dim3 grid_o((unsigned)(rows8 * ((2 * tiles_own + MC_JOIN_WPB - 1) / MC_JOIN_WPB) * 8)), block_o(64 * MC_JOIN_WPB);
-		if (ks <= 8) hipLaunchKernelGGL((join_owner_kernel<8>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own);
-		else if (ks <= 16) hipLaunchKernelGGL((join_owner_kernel<16>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own);
-		else hipLaunchKernelGGL((join_owner_kernel<32>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own);
+		const dim3 grid_o((unsigned)(rows8 * ((nside * tiles_own + MC_JOIN_WPB - 1) / MC_JOIN_WPB) * 8)), block_o(64 * MC_JOIN_WPB);
+		if (ks <= 8) hipLaunchKernelGGL((join_owner_kernel<8>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own, sides);
+		else if (ks <= 16) hipLaunchKernelGGL((join_owner_kernel<16>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own, sides);
+		else hipLaunchKernelGGL((join_owner_kernel<32>), grid_o, block_o, 0, st, fL, fR, volL, volR, C, D, ds, H, W, tiles_own, sides);
 		what = "stereo_join_hwd (owner tiles)";
 	} else {   // C > 64 (ks > 32, MC_JOIN_MAX_C = 128: ks <= 64)
 		const int tiles = (W + D - 1 + 31) / 32;  // incl. the virtual tiles right of the image (right volume's NaN triangle)
@@ -435,7 +443,7 @@ int stereo_join_hwd(const float *fL, const float *fR, float *volL, float *volR, 
 	}
 	const int rc = check_launch(what);
 	if (rc || n <= 0) return rc;
-	hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)2 * H * n * 64, 256)), block, 0, st, volL, volR, D, ds, H, W, n);
+	hipLaunchKernelGGL(fix_border_hwd_kernel, dim3(cdiv((int64_t)nside * H * n * 64, 256)), block, 0, st, volL, volR, D, ds, H, W, n, sides);
 	return check_launch("fix_border_hwd");
 }
 

@@ -3,15 +3,22 @@
 `fc_cost_volumes(feat, layers, disp_max)` -> (volL, volR), each (1,D,H,W): NaN-filled (main.lua:966), with
 net_te2(concat(featL[:,y,x], featR[:,y,x-d])) at volL[d,y,x] and volR[d,y,x-d] -- the raw volumes `stereo_predict`
 continues from (fix_border is applied by the caller, main.lua:979).  `layers` = [(weight (out,in), bias (out)), ...] as
-CUDA float tensors: the nn.SpatialConvolution1_fw weights of net_te2 (main.lua:688-695)."""
+CUDA float tensors: the nn.SpatialConvolution1_fw weights of net_te2 (main.lua:688-695).
+
+`mode`: "fp32" (the default) is `mc_fc_stack` of libmcadcensus.so, exact fp32 products on the fp32 MFMA; "bf16x3" is
+`mc_fc_split_stack` of libmcfcsplit.so, whose hidden layers take every product as three bf16 products of hi + lo parts
+(include/mc_fc_split.h states the arithmetic; within 1e-5 of "fp32" on sigmoid outputs)."""
 import ctypes as C
 
 import torch
 
 from ._lib import check, lib
+from .train_common import FC_MODES
 
 
-def fc_cost_volumes(feat, layers, disp_max, workspace=None):
+def fc_cost_volumes(feat, layers, disp_max, workspace=None, mode="fp32"):
+    if mode not in FC_MODES:
+        raise ValueError("fc mode %r: one of %s" % (mode, " | ".join(FC_MODES)))
     feat = feat.contiguous()
     _, Cn, H, W = feat.shape
     D = int(disp_max)
@@ -23,7 +30,13 @@ def fc_cost_volumes(feat, layers, disp_max, workspace=None):
             raise TypeError("contiguous float32 CUDA tensors expected")
     if ws[0].shape[1] != 2 * Cn:
         raise ValueError("layer 0 expects %d inputs, features give %d" % (ws[0].shape[1], 2 * Cn))
-    need = lib.mc_fc_stack_workspace_bytes(Cn, n, H, W)
+    if mode == "bf16x3":
+        from . import _fc_split_lib
+        split = _fc_split_lib.load()
+        workspace_bytes, stack, check_rc = split.mc_fc_split_workspace_bytes, split.mc_fc_split_stack, _fc_split_lib.check
+    else:
+        workspace_bytes, stack, check_rc = lib.mc_fc_stack_workspace_bytes, lib.mc_fc_stack, check
+    need = workspace_bytes(Cn, n, H, W)
     if workspace is None or workspace.numel() < need + 16:
         workspace = torch.empty(need + 16, dtype=torch.uint8, device=feat.device)
     wsp = workspace.data_ptr() + (-workspace.data_ptr()) % 16
@@ -32,6 +45,6 @@ def fc_cost_volumes(feat, layers, disp_max, workspace=None):
     wp = (C.c_void_p * n)(*[w.data_ptr() for w in ws])
     bp = (C.c_void_p * n)(*[b.data_ptr() for b in bs])
     widths = (C.c_int * n)(*[w.shape[0] for w in ws])
-    check(lib.mc_fc_stack(feat[0].data_ptr(), feat[1].data_ptr(), Cn, H, W, D, wp, bp, widths, n, vl.data_ptr(), vr.data_ptr(),
-                          wsp, need, torch.cuda.current_stream().cuda_stream), "fc_stack")
+    check_rc(stack(feat[0].data_ptr(), feat[1].data_ptr(), Cn, H, W, D, wp, bp, widths, n, vl.data_ptr(), vr.data_ptr(),
+                   wsp, need, torch.cuda.current_stream().cuda_stream), "fc_stack" if mode == "fp32" else "fc_split_stack")
     return vl, vr

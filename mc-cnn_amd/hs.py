@@ -209,7 +209,11 @@ def parse(argv):
     ap.add_argument("-gpu", type=int, default=1, help="1-based, as main.py's")
     ap.add_argument("-no_reuse", action="store_true", help="run the whole pipeline for every candidate (no blur-only reuse)")
     ap.add_argument("-l1", type=int, default=None, help="arch fast: the convolutions of NET_FNAME, 1..5, where not the data set's")
+    from .train_common import add_fc_mode_flag
+    add_fc_mode_flag(ap)             # main.py's flag: arch slow's cost stage through mc_fc_stack (fp32) or mc_fc_split_stack (bf16x3)
     opt = ap.parse_args(argv)
+    if opt.fc_mode != "fp32" and opt.arch != "slow":
+        raise SystemExit("hs: -fc_mode %s for arch %s: only arch slow has an FC stack (main.py -fc_mode)" % (opt.fc_mode, opt.arch))
     if opt.l1 is not None and (opt.arch != "fast" or not 1 <= opt.l1 <= 5):
         raise SystemExit("hs: -l1 %d for arch %s: -l1 1..5 names the depth of a fast net (main.py -l1); the other archs keep "
                          "their data set's" % (opt.l1, opt.arch))

@@ -9,7 +9,8 @@ convolutions are `mc_conv3x3`, a hand-written fp32-MFMA implicit GEMM of libmcad
 pipeline in one `mc_predict` call, and writes `left.bin`, `right.bin` (1,D,H,W) and `disp.bin` (1,1,H,W), raw float32,
 with the reference's messages.  `-a time` is main.lua:1140-1167 (min of N runs on an uninitialised batch).
 
-Architectures: fast, slow (feature net + `mc_fc_stack`, main.lua:958-983), ad and census (no net: `mc_ad` / `mc_census_ws`
+Architectures: fast, slow (feature net + `mc_fc_stack`, main.lua:958-983; `-fc_mode bf16x3` takes the FC stack's products as three
+bf16 products each, `mc_fc_split_stack` of libmcfcsplit.so, wherever arch slow predicts; the default `-fc_mode fp32` is `mc_fc_stack`), ad and census (no net: `mc_ad` / `mc_census_ws`
 volumes from the image pair, main.lua:932-942).
 
 -net_fname: the reference's Torch7 `net_*.t7` (main.lua:892-902; read by `t7.py`), an `.npz` with arrays
@@ -43,7 +44,7 @@ import numpy as np
 
 from .binio import write_bin
 from .params import NET_SHAPES, TABLES
-from .train_common import add_net_flags, check_net_flags, new_parser, pipeline_prm, refuse_net_flags
+from .train_common import add_fc_mode_flag, add_net_flags, check_fc_mode, check_net_flags, new_parser, pipeline_prm, refuse_net_flags
 
 
 def rgb2y(img):
@@ -84,6 +85,7 @@ def parse(argv):
     ap.add_argument("-right", default="")
     ap.add_argument("-disp_max", type=int, default=228 if dataset != "mb" else 200)
     ap.add_argument("-tiny", action="store_true")
+    add_fc_mode_flag(ap)
     ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
     if dataset in ("kitti", "kitti2015"):
         ap.add_argument("-at", type=int, default=0, choices=(0, 1),
@@ -91,6 +93,7 @@ def parse(argv):
     opt = ap.parse_args(argv[2:])
     if arch == "fast":
         check_net_flags(opt, "main.py")
+    check_fc_mode(opt, arch, "main.py")
     if opt.a not in ("predict", "time") and (opt.a not in TRAIN_ACTIONS or dataset not in ("kitti", "kitti2015") or arch != "fast"):
         raise SystemExit("main.py: -a %s is not supported for %s %s; training and testing cover -a %s for "
                          "{kitti|kitti2015} fast only (arch slow trains through train_slow.parse, which main() routes "
@@ -187,13 +190,14 @@ def features_slow(x_batch, layers):
     return h
 
 
-def raw_volumes_slow(feat, fc_layers, disp_max, border_n):
-    """main.lua:958-983: the FC stack for every (pixel, disparity) -> NaN-filled volumes, then fix_border."""
+def raw_volumes_slow(feat, fc_layers, disp_max, border_n, fc_mode="fp32"):
+    """main.lua:958-983: the FC stack for every (pixel, disparity) -> NaN-filled volumes, then fix_border.  fc_mode: fc.fc_cost_volumes'
+    mode, "fp32" (mc_fc_stack) or "bf16x3" (mc_fc_split_stack)."""
     import torch
     from . import adcensus
     from .fc import fc_cost_volumes
     dl = [(torch.from_numpy(w).to(feat.device), torch.from_numpy(b).to(feat.device)) for w, b in fc_layers]
-    vl, vr = fc_cost_volumes(feat, dl, disp_max)
+    vl, vr = fc_cost_volumes(feat, dl, disp_max, mode=fc_mode)
     adcensus.fix_border(vl, border_n, -1)
     adcensus.fix_border(vr, border_n, 1)
     return vl, vr
@@ -270,7 +274,7 @@ def main(argv=None):
         if arch == "fast":
             return stereo_predict_fused(x_batch, prm, D, feat=features_fast(x_batch, layers), workspace=workspace,
                                         want_volumes=want_volumes)
-        raw = raw_volumes_slow(features_slow(x_batch, layers), fc_layers, D, prm["border_n"])
+        raw = raw_volumes_slow(features_slow(x_batch, layers), fc_layers, D, prm["border_n"], fc_mode=getattr(opt, "fc_mode", "fp32"))
         return stereo_predict_fused(x_batch, prm, D, raw=raw, workspace=workspace, want_volumes=want_volumes)
     if opt.a in TRAIN_ACTIONS:
         if mod is None:

@@ -92,6 +92,29 @@ def check_net_flags(opt, who):
                          % ((who, opt.ks) + L1_TRAINABLE))
 
 
+FC_MODES = ("fp32", "bf16x3")      # fc.fc_cost_volumes: mc_fc_stack | mc_fc_split_stack (include/mc_fc_split.h)
+
+
+def add_fc_mode_flag(ap):
+    """-fc_mode: how arch slow's FC stack takes its products wherever a command line predicts (-a predict | time | test_te | test_all,
+    the test_te after train_tr included).  Not a flag of main.lua; the default is today's fp32 kernel."""
+    ap.add_argument("-fc_mode", default="fp32", choices=FC_MODES,
+                    help="arch slow's FC stack: fp32 (mc_fc_stack, exact products) or bf16x3 (mc_fc_split_stack, three bf16 products each)")
+
+
+def check_fc_mode(opt, arch, who):
+    """-fc_mode bf16x3 where there is no FC stack: refused, naming where it applies.  -fc_mode fp32 is taken there and means nothing, so
+    it leaves opt as it is without the flag."""
+    if arch == "slow":
+        return
+    mode = opt.__dict__.pop("fc_mode", "fp32")
+    if mode != "fp32":
+        opt.fc_mode = mode
+        raise SystemExit("%s: -fc_mode %s is not supported for arch %s: it has no FC stack (%s); -fc_mode fp32 | bf16x3 is a flag of "
+                         "arch slow" % (who, opt.fc_mode, arch, "the fast net's cost is StereoJoin's dot product" if arch == "fast"
+                                        else "its cost is computed from the image pair"))
+
+
 def pipeline_prm(t, opt):
     """The hyper-parameter table of the post-CNN pipeline: t with the 13 flags and the stage switches of opt."""
     prm = dict(t)

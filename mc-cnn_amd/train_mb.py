@@ -56,12 +56,14 @@ def parse_mb(argv, arch, train_defaults, who):
     ap.add_argument("-data_dir", default="", help="default data.mb.<rect>_<color> (main.lua:456)")
     ap.add_argument("-subset", type=float, default=1.0, help="main.lua:28; only 1 is supported")
     ap.add_argument("-debug", action="store_true", help="main.lua:18; not supported")
+    common.add_fc_mode_flag(ap)       # arch slow: the test_te it runs, the one after train_tr included (main.main's run)
     common.refuse_net_flags(argv, who)
     if arch == "fast":
         common.add_net_flags(ap, "mb", arch)       # -l1 other than 5 trains through train_depth.py: main.route
     opt = ap.parse_args(argv[2:])
     if arch == "fast":
         common.check_net_flags(opt, who)
+    common.check_fc_mode(opt, arch, who)
     if opt.a == "test_all":
         raise SystemExit("%s: -a test_all is not supported on Middlebury (main.lua:1136 asserts the same)" % who)
     if opt.a == "submit":

@@ -2,7 +2,7 @@
 """Candidates per second of the parameter search (mc_cnn_amd/hs.py) on a device-resident test set, against what the search would
 cost through `main.run` + `train.evaluate` per candidate.
 
-    python scripts/hs_bench.py [--out FILE] [--pairs 40] [--arch fast slow] [--candidates 8] [--rounds 3]
+    python scripts/hs_bench.py [--out FILE] [--pairs 40] [--arch fast slow] [--candidates 8] [--rounds 3] [--fc_mode fp32|bf16x3] [--setup_only]
 
 The set is synthetic and KITTI-sized: --pairs test pairs of 350 x 1242 (read 1224 .. 1242 wide, as KITTI's images are), disp_max 228,
 textured scenes with piecewise-constant disparity, ground truth known on two thirds of the pixels, seeded random nets.  The nets
@@ -17,7 +17,8 @@ Per arch, in one process:
   * the baseline: `train.evaluate` with the `run` main.main builds for the arch (cost stage recomputed, per-pair synchronise, .cpu()
     and numpy error), for the same candidates, and that its mean equals EvalSet's bit for bit;
   * mc_eval_error's time per call at 350 x 1226 against a 1242-wide ground truth (device events around back-to-back launches).
-Times are host clocks around work that ends in a device synchronise.
+Times are host clocks around work that ends in a device synchronise.  --fc_mode is hs.py's -fc_mode for arch slow (the cost stage's FC
+stack); --setup_only stops an arch after its set-up line.
 """
 import argparse
 import contextlib
@@ -72,13 +73,16 @@ def bench_arch(arch, data, a, say):
     from mc_cnn_amd.predict import stereo_predict_fused
     dev = torch.device("cuda", 0)
     net = "random:3"
-    opt = hs.parse(["random", "kitti", arch, "test_te", net, "-disp_max", str(D)])
+    fc_mode = a.fc_mode if arch == "slow" else "fp32"
+    opt = hs.parse(["random", "kitti", arch, "test_te", net, "-disp_max", str(D), "-fc_mode", fc_mode])
     layers, fc = hs.check_net(net, "kitti", arch)
     grid = hs.grid_of("kitti", arch)
     t_setup, es = timed(lambda: EvalSet("kitti", arch, opt, layers, fc, dev, 48 << 30, data=data))
     held = 4 * sum(e["H"] * e["W"] for e in es.examples)
-    say("%s: set-up %.2f s; resident: cost stage %.2f GB (%d of %d pairs), post-median maps %.3f GB"
-        % (arch, t_setup, es.resident_bytes / 1e9, es.n_cached, es.n, held / 1e9))
+    say("%s%s: set-up %.2f s; resident: cost stage %.2f GB (%d of %d pairs), post-median maps %.3f GB"
+        % (arch, "" if fc_mode == "fp32" else " -fc_mode " + fc_mode, t_setup, es.resident_bytes / 1e9, es.n_cached, es.n, held / 1e9))
+    if a.setup_only:
+        return
     rng = random.Random(7)
     cands = []
     while len(cands) < a.candidates:
@@ -134,7 +138,7 @@ def bench_arch(arch, data, a, say):
         def run(x_batch, Dm):
             if arch == "fast":
                 return stereo_predict_fused(x_batch, prm, Dm, feat=main.features_fast(x_batch, dl))
-            return stereo_predict_fused(x_batch, prm, Dm, raw=main.raw_volumes_slow(main.features_slow(x_batch, dl), fc, Dm, prm["border_n"]))
+            return stereo_predict_fused(x_batch, prm, Dm, raw=main.raw_volumes_slow(main.features_slow(x_batch, dl), fc, Dm, prm["border_n"], fc_mode=fc_mode))
         with contextlib.redirect_stdout(io.StringIO()):
             return train.evaluate("kitti", opt, run, dev, data=data)
     n_base = a.candidates if arch == "fast" else 1
@@ -178,6 +182,8 @@ def main(argv=None):
     ap.add_argument("--arch", nargs="+", default=["fast", "slow"], choices=["fast", "slow"])
     ap.add_argument("--candidates", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--fc_mode", default="fp32", choices=["fp32", "bf16x3"], help="arch slow: hs.py's -fc_mode")
+    ap.add_argument("--setup_only", action="store_true", help="per arch, the set-up line only")
     a = ap.parse_args(argv)
     import torch
     assert torch.cuda.is_available(), "hs_bench.py measures on the GPU"

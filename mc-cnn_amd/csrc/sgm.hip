@@ -41,13 +41,16 @@ struct SgmPassArgs {
 	int direction[2];
 	int nvol;
 	int H, W, D, ds;
-	int tri;              // 1: the caller's promise about the volumes' NaN triangle (sgm_sweeps): the vertical fused sweeps leave it alone
+	int tri;              // 1: the caller's promise about the volumes' NaN triangle (sgm_sweeps): the fused sweeps leave it alone where nothing reads it
 	                      // (in the padding in front of cls0: every other field keeps its offset, and the other instances their code)
 	const uint8_t *cls0;  // [4][cls_plane], plane = H*W bytes padded to a dword multiple
 	int64_t cls_plane;
 	const uint8_t *win;   // [2][4][H][Wm]
 	int Wm;
 	float P1[3], P2[3], P1a[3];  // 0: both < tau, 1: mixed, 2: both > tau ; P1a = P1 / alpha1
+	int drop_h[2];        // the horizontal launch under `tri`: 1: nothing reads out[v]'s NaN triangle (the volume's final costs are dropped), it is not stored
+	                      // (drop_out is set after that launch and drops whole runs.  The struct has no padding left: behind the last field, so that
+	                      // every other field keeps its offset, and the other instances their code)
 };
 
 __device__ __forceinline__ int cls_of(float v, float tau) { return v < tau ? 0 : (v > tau ? 2 : 1); }
@@ -155,9 +158,20 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t pixel_rsrc(const float *base, 
 //   reference, ((0 + L_0) + L_1) + L_2) + L_3, is restored by MODE 3.
 // U = steps kept in flight per wave (register ring): the scan is a strict recurrence, so memory latency is
 //   covered by prefetch depth, not by occupancy.
-template <int DIRN, int VPL, int MODE, bool ARGMIN, bool VEC, int U, bool DUAL, bool FAR>
+// TRIH (the DUAL launch under A.tri; VEC and not FAR only): the horizontal sweeps leave the NaN triangle alone where nothing reads it.
+//   A horizontal line crosses the triangle, so the live count is a property of the STEP: at column x, Dv(s) = min(D, x + 1) (direction -1)
+//   or min(D, W - x) (direction +1), wave-uniform.  A lane's 16-byte piece that starts at or beyond Dv(s) * 4 bytes (the vertical sweeps'
+//   rule: a piece that straddles Dv moves whole) gets the out-of-range offset for that step's load of C, and its c[] is set to NaN in
+//   registers -- what memory holds there by the promise, so the recurrence, prev, m and every stored value are the bits of TRIH = false.
+//   out2 (the second direction) and the out of a volume with A.drop_h set are not stored in those pieces either; any other out is
+//   stored whole, NaNs included (exports, sub-pixel refinement and the next SGM iteration read them).  The cost: per step one scalar
+//   multiply-add, compare and select per use (load, recurrence, store), and per piece a v_cmp against that scalar with one select per
+//   offset and four on c[].  The per-element and the FAR instances and every launch without the promise run TRIH = false, the code as
+//   it was.
+template <int DIRN, int VPL, int MODE, bool ARGMIN, bool VEC, int U, bool DUAL, bool FAR, bool TRIH>
 __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 {
+	static_assert(!TRIH || (DIRN == 0 && DUAL && MODE == 0 && VEC && !FAR && !ARGMIN), "TRIH: the fused horizontal launch only");
 	constexpr int NACC = MODE == 0 ? 0 : (MODE == 3 ? 2 : 1);
 	const int lane = threadIdx.x & 63;
 	const int H = A.H, W = A.W, D = A.D, ds = A.ds, Wm = A.Wm;
@@ -244,15 +258,28 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 		lane_off[q] = ((FAR && !TRI) || b < live_bytes) ? b : OOBV;
 	}
 	const unsigned lane0_off = lane == 0 ? 0u : OOBV;
+	// TRIH: the live bytes of step s's run, Dv(s) * 4 in a trimmed column and the whole run elsewhere (Dv(s) = hdv0 + s * hdv1 >= 1, scalar)
+	const int hdv0 = direction < 0 ? x0s + 1 : W - x0s, hdv1 = direction < 0 ? sx : -sx;
+	// whose stores leave the triangle out: the second direction's (out2) and those of a volume whose final costs are dropped; the others
+	// take the same straight-line code with a count that never falls below D
+	const bool trim_st = TRIH && (second || A.drop_h[v] != 0);
+	const int sdv0 = trim_st ? hdv0 : D, sdv1 = trim_st ? hdv1 : 0;
+	auto live_bytes_of = [&](int dv) -> unsigned { return dv < D ? (unsigned)dv * 4u : (unsigned)run_bytes; };
+	auto live_at = [&](int s) -> unsigned { return live_bytes_of(hdv0 + s * hdv1); };
+	// a piece's offset at a step with `lim` live bytes (lim <= run_bytes: this is lane_off[q] where lim is the whole run)
+	auto piece_off = [&](int q, unsigned lim) -> unsigned {
+		const unsigned b = (unsigned)(dbase + 4 * q) * 4u;
+		return b < lim ? b : OOBV;
+	};
 
-	// rs: the volume's descriptor (FAR: ignored), so: the pixel's scalar byte offset (FAR: ignored)
-	auto load_run = [&](float (&dst)[VPL], const float *base, const __amdgpu_buffer_rsrc_t &rs, unsigned so, int64_t pix) {
+	// rs: the volume's descriptor (FAR: ignored), so: the pixel's scalar byte offset (FAR: ignored); lim (TRIH): the run's live bytes
+	auto load_run = [&](float (&dst)[VPL], const float *base, const __amdgpu_buffer_rsrc_t &rs, unsigned so, int64_t pix, unsigned lim = 0u) {
 		const __amdgpu_buffer_rsrc_t r = FAR ? pixel_rsrc(base, pix * ds, run_bytes) : rs;
 		const unsigned soff = FAR ? 0u : so;
 		if (VEC) {
 #pragma unroll
 			for (int q = 0; q < VPL / 4; ++q) {
-				const uint4v t = __builtin_amdgcn_raw_buffer_load_b128(r, lane_off[q], soff, MC_SGM_VOL_AUX);
+				const uint4v t = __builtin_amdgcn_raw_buffer_load_b128(r, TRIH ? piece_off(q, lim) : lane_off[q], soff, MC_SGM_VOL_AUX);
 				dst[4 * q + 0] = __uint_as_float(t.x); dst[4 * q + 1] = __uint_as_float(t.y);
 				dst[4 * q + 2] = __uint_as_float(t.z); dst[4 * q + 3] = __uint_as_float(t.w);
 			}
@@ -265,7 +292,7 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 	auto load_step = [&](StepData<VPL, NACC> &sd, int s) {
 		const unsigned so = c0v + (unsigned)s * c1v;
 		const int64_t pix = FAR ? (int64_t)(y0s + s * sy) * W + (x0s + s * sx) : 0;
-		load_run(sd.c, Cp, rC, so, pix);
+		load_run(sd.c, Cp, rC, so, pix, TRIH ? live_at(s) : 0u);
 		if constexpr (NACC >= 1) load_run(sd.a, Ain, rA, so, pix);
 		if constexpr (NACC >= 2) load_run(sd.a2, Ain2, rA2, so, pix);
 		unsigned pk = 0;
@@ -280,13 +307,14 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 		const int64_t pix = FAR ? (int64_t)(y0s + s * sy) * W + (x0s + s * sx) : 0;
 		const __amdgpu_buffer_rsrc_t r = FAR ? pixel_rsrc(Out, pix * ds, drop ? 0 : run_bytes) : rO;
 		const unsigned soff = FAR ? 0u : c0v + (unsigned)s * c1v;
+		const unsigned lim = TRIH ? live_bytes_of(sdv0 + s * sdv1) : (unsigned)run_bytes;
 		if (VEC) {
 #pragma unroll
 			for (int q = 0; q < VPL / 4; ++q) {
 				uint4v t;
 				t.x = __float_as_uint(o[4 * q + 0]); t.y = __float_as_uint(o[4 * q + 1]);
 				t.z = __float_as_uint(o[4 * q + 2]); t.w = __float_as_uint(o[4 * q + 3]);
-				__builtin_amdgcn_raw_buffer_store_b128(t, r, lane_off[q], soff, MC_SGM_ST_AUX);
+				__builtin_amdgcn_raw_buffer_store_b128(t, r, TRIH ? piece_off(q, lim) : lane_off[q], soff, MC_SGM_ST_AUX);
 			}
 		} else {
 #pragma unroll
@@ -328,7 +356,14 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 
 	// keep != nullptr: the step's outputs go there instead of to memory (the horizontal sweeps' batched stores below)
 	auto process = [&](const StepData<VPL, NACC> &sd, int s, float *keep = nullptr) {
-		float val[VPL], o[VPL];
+		float val[VPL], o[VPL], c[VPL];
+#pragma unroll
+		for (int j = 0; j < VPL; ++j) c[j] = sd.c[j];
+		if (TRIH) {   // the pieces this step's load left out: NaN, as C holds there
+			const unsigned lim = live_at(s);
+#pragma unroll
+			for (int j = 0; j < VPL; ++j) c[j] = (unsigned)(dbase + (j & ~3)) * 4u < lim ? c[j] : __builtin_nanf("");
+		}
 		const int a0 = __builtin_amdgcn_readfirstlane((int)sd.a0);
 		const int amatch = a0 == 1 ? 3 : a0;
 		// scalar selects, as written: the compiler sends a select of two float SGPRs to the VALU (two moves and a v_cndmask each)
@@ -359,12 +394,12 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 			asm("v_min_f32 %0, %1, %2\n\tv_min3_f32 %0, %0, %3, %4"
 			    : "=&v"(cost)
 			    : "v"(prev[j]), "v"(m + P2), "v"(pm + (DIRN == 2 ? P1a : P1)), "v"(pp + (DIRN == 3 ? P1a : P1)));
-			val[j] = (sd.c[j] + cost) - m;  // adcensus.cu:615
+			val[j] = (c[j] + cost) - m;  // adcensus.cu:615
 		}
 		if (s == 0) {   // border branch, adcensus.cu:567-572: L_r = C.  A uniform branch taken once per line, not VPL selects per step
 			asm volatile("; border step");
 #pragma unroll
-			for (int j = 0; j < VPL; ++j) val[j] = sd.c[j];
+			for (int j = 0; j < VPL; ++j) val[j] = c[j];
 		}
 		float q[VPL];
 #pragma unroll
@@ -436,7 +471,16 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 template <int DIRN, int VPL, int MODE, bool ARGMIN, bool VEC, int U, bool DUAL, bool FAR>
 __global__ void __launch_bounds__(256) sgm_pass_kernel(const SgmPassArgs A)
 {
-	sgm_line<DIRN, VPL, MODE, ARGMIN, VEC, U, DUAL, FAR>(A, __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)));
+	const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+	// the fused horizontal launch holds both forms of its line walk and takes the trimmed one under the caller's promise (one uniform branch
+	// per wave); without it, and in every other instance, the walk is the code it was
+	if constexpr (DIRN == 0 && DUAL && MODE == 0 && VEC && !FAR && !ARGMIN) {
+		if (A.tri) {
+			sgm_line<DIRN, VPL, MODE, ARGMIN, VEC, U, DUAL, FAR, true>(A, wave);
+			return;
+		}
+	}
+	sgm_line<DIRN, VPL, MODE, ARGMIN, VEC, U, DUAL, FAR, false>(A, wave);
 }
 
 // ---------------------------------------------------------------------------
@@ -544,10 +588,13 @@ static void launch_pass(const SgmPassArgs &A, bool vec, hipStream_t st)
 //                  left as the down sweep wrote it, the arg-min disp[v] is written as before.
 //                  tri (fused only) is the caller's promise that, for every volume v, C[v] is NaN at every (pixel, d) with
 //                  d >= Dv, Dv = min(D, x + 1) for direction[v] < 0 and min(D, W - x) for direction[v] > 0 (the voxels whose
-//                  partner pixel lies outside the image).  The horizontal launch then writes NaN there into out and out2, and the
-//                  two vertical launches, which work in place on out, neither read nor write those voxels: every buffer
-//                  holds what it holds without the promise, except the padding d in [D, ds) of a trimmed column, which
-//                  keeps the horizontal launch's values (nothing reads the padding).
+//                  partner pixel lies outside the image).  No launch then loads those voxels of C, out or out2 (whole 16-byte pieces
+//                  at or beyond Dv; a piece that straddles Dv moves whole).  The horizontal launch writes NaN there into out, as
+//                  without the promise; it does not store them into out2, nor into the out of a volume in drop_final.  The two
+//                  vertical launches, which work in place on out, neither read nor write them.  So out and disp hold what they
+//                  hold without the promise, except: the padding d in [D, ds) of a trimmed column (the horizontal launch's values,
+//                  NaN where the piece was not loaded), out2's triangle and the triangle in the out of a volume in drop_final
+//                  (both keep what the buffers held before the call).  All three are unspecified and read by nothing.
 int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
                const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,
                float alpha1, float q1, float q2, bool fused, unsigned drop_final, bool tri, hipStream_t st)
@@ -565,6 +612,8 @@ int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2
 		A.disp[v] = disp ? disp[k] : nullptr;
 		A.direction[v] = direction[k];
 		A.drop_out[v] = 0;
+		// (drop_final arrives with the last iteration only: an earlier iteration's out keeps its NaNs, the next one's promise about its input)
+		A.drop_h[v] = (fused && tri && v < nvol && ((drop_final >> v) & 1)) ? 1 : 0;
 	}
 	A.nvol = nvol;
 	A.tri = (fused && tri) ? 1 : 0;

@@ -18,34 +18,31 @@
 // activation it is masked by, in place: a layer's activations are dead once its weight gradient is taken.
 // GEMMs with only two 32 x 32 output tiles (layer 3 / 4 forward, layer 4 data gradient) split K over four waves and
 // add the partial tiles in a fixed order.
-// The GEMMs, the layer chain, the LDS layout and the update are train_conv.h's, derived from the net described below and
-// shared with train_mb.hip; the host checks and the run driver are train_net.h's.  This file holds the net, its kernels'
-// entries and the entry points.
+// The GEMMs, the layer chain, the LDS layout and the update are train_conv.h's; the net, the kernels' bodies, the launches of a
+// step and the checks of the entry points are train_fast.h's, which states them once for this library, libmctrainmb.so and
+// libmctraindepth.so; the run driver is train_net.h's.  This file holds the library's tag, its pinned layout, its kernels'
+// entries and its entry points.
 #include "mc_common.h"
 #include "../../include/mc_train.h"
-#include "train_sampler.h"
-#include "train_conv.h"   // the GEMMs, the step of a net, the update
+#include "train_fast.h"   // the fast net, its kernels' bodies, the host side of a step
 
 namespace mc {
 
-struct Net {
-	static constexpr int FM = MC_TRAIN_FM, PS = MC_TRAIN_WS, NL = MC_TRAIN_L1, NP = 3, L2 = 0, MAX_PAIRS = MC_TRAIN_MAX_PAIRS;
+struct Lib {
 	static constexpr const char *PREFIX = "train";
+	static constexpr int MAX_PAIRS = MC_TRAIN_MAX_PAIRS;
 };
-constexpr int NPRM = MC_TRAIN_NPRM;
-constexpr int NPARAMS = MC_TRAIN_NPARAMS;
-static_assert(n_conv<Net>() == NPARAMS && off_b<Net>(4) + FM == NPARAMS, "parameter layout: w1 b1 w2 b2 w3 b3 w4 b4");
+using Net = FastNet<MC_TRAIN_L1, Lib>;
+static_assert(Net::FM == MC_TRAIN_FM && Net::PS == MC_TRAIN_WS && NPRM == MC_TRAIN_NPRM && Net::SAMPLE_NT == 256, "the net of mc_train.h");
+static_assert(Net::NPARAMS == MC_TRAIN_NPARAMS && off_b<Net>(4) + FM == Net::NPARAMS, "parameter layout: w1 b1 w2 b2 w3 b3 w4 b4");
 // LDS: X [3][81] in 256 floats, A1 [3][64][49], A2 [3][64][25], A3 [3][64][9], A4 [3][64], the partial tiles [8][16][64]
-constexpr size_t LDS_BYTES = STEP_LDS_BYTES<Net>;
-static_assert(LDS_BYTES == 98304 && lds_act<Net>(1) == 256, "the LDS layout");
+static_assert(Net::LDS_BYTES == 98304 && lds_act<Net>(1) == 256, "the LDS layout");
 
 __global__ void __launch_bounds__(256) train_sample_kernel(const float *__restrict__ x0, const float *__restrict__ x1, int n_img, int H, int W,
                                                            const float *__restrict__ nnz, int64_t n_nnz, const int32_t *__restrict__ rows,
                                                            const float *__restrict__ prm, float *__restrict__ out)
 {
-	const int pair = blockIdx.x, t = threadIdx.x;
-	if (t < 3 * WS * WS)
-		out[(int64_t)pair * 3 * WS * WS + t] = sample_pair_pixel<WS>(x0, x1, n_img, H, W, nnz, n_nnz, rows[pair], prm + (int64_t)pair * NPRM, t);
+	write_patches<Net, ImageStore>(out, x0, x1, n_img, H, W, nnz, n_nnz, rows, prm);
 }
 
 // Kernel (a): one workgroup per pair.  SAMPLE: the patches come from the images (rows[pair] of nnz, prm of the pair);
@@ -57,16 +54,7 @@ __global__ void __launch_bounds__(NT) train_step_kernel(const float *__restrict_
                                                         const float *__restrict__ prm, const float *__restrict__ params,
                                                         float margin, int pow, float inv_pairs, float *__restrict__ slab, float *__restrict__ losses)
 {
-	extern __shared__ __attribute__((aligned(16))) float lds[];
-	const int pair = blockIdx.x, t = threadIdx.x;
-	if (t < 3 * WS * WS) {
-		if (SAMPLE)
-			lds[t] = sample_pair_pixel<WS>(x0, x1, n_img, H, W, nnz, n_nnz, rows[pair], prm + (int64_t)pair * NPRM, t);
-		else
-			lds[t] = patches[(int64_t)pair * 3 * WS * WS + t];
-	}
-	__syncthreads();
-	pair_step<Net>(params, margin, pow, inv_pairs, lds, slab + (int64_t)pair * NPARAMS, losses + pair);
+	step_of_pair<Net, SAMPLE, ImageStore>(patches, params, margin, pow, inv_pairs, slab, losses, x0, x1, n_img, H, W, nnz, n_nnz, rows, prm);
 }
 
 // Kernel (b): g = sum over pairs in order; v = mom * v - lr * g; w += v.  Block 0 also writes the mean loss.
@@ -74,12 +62,12 @@ __global__ void __launch_bounds__(256) train_sgd_kernel(const float *__restrict_
                                                         float *__restrict__ params, float *__restrict__ moms, float lr, float mom,
                                                         float *__restrict__ loss_out)
 {
-	slab_sgd(slab, pair_losses, n_pairs, NPARAMS, params, moms, lr, mom, loss_out);
+	slab_sgd(slab, pair_losses, n_pairs, Net::NPARAMS, params, moms, lr, mom, loss_out);
 }
 
 static int prepare_step_kernels()
 {
-	return prepare_kernels(Net::PREFIX, {(const void *)train_step_kernel<true>, (const void *)train_step_kernel<false>}, LDS_BYTES);
+	return raise_lds_limit<Net>({(const void *)train_step_kernel<true>, (const void *)train_step_kernel<false>});
 }
 
 }  // namespace mc
@@ -101,37 +89,16 @@ int mc_train_sample(const float *x0, const float *x1, int n_img, int H, int W, c
                     const float *prm, int n_pairs, float *out, void *stream)
 {
 	if (int rc = check_image_args(Net::PREFIX, x0, x1, n_img, H, W, nnz, n_nnz)) return rc;
-	MC_REQUIRE(n_pairs >= 1 && n_pairs <= (1 << 24), "train_sample: n_pairs %d", n_pairs);
-	MC_REQUIRE(rows && prm && out, "train_sample: null pointer");
-	train_sample_kernel<<<n_pairs, 256, 0, as_stream(stream)>>>(x0, x1, n_img, H, W, nnz, n_nnz, rows, prm, out);
-	return check_launch("train_sample");
-}
-
-static int enqueue_step(const float *patches, const float *x0, const float *x1, int n_img, int H, int W, const float *nnz, int64_t n_nnz,
-                        const int32_t *rows, const float *prm, int n_pairs, float *params, float *moms, float lr, float mom, float margin,
-                        int pow, float *loss_out, void *ws, hipStream_t st)
-{
-	float *slab = (float *)ws;
-	float *pair_losses = slab + (size_t)n_pairs * NPARAMS;
-	if (patches)
-		train_step_kernel<false><<<n_pairs, NT, LDS_BYTES, st>>>(patches, x0, x1, n_img, H, W, nnz, n_nnz, rows, prm, params, margin,
-		                                                               pow, 1.f / (float)n_pairs, slab, pair_losses);
-	else
-		train_step_kernel<true><<<n_pairs, NT, LDS_BYTES, st>>>(patches, x0, x1, n_img, H, W, nnz, n_nnz, rows, prm, params, margin,
-		                                                              pow, 1.f / (float)n_pairs, slab, pair_losses);
-	if (int rc = check_launch("train_step")) return rc;
-	train_sgd_kernel<<<cdiv(NPARAMS, 256), 256, 0, st>>>(slab, pair_losses, n_pairs, params, moms, lr, mom, loss_out);
-	return check_launch("train_sgd");
+	return sample_patches<Net, train_sample_kernel>("train_sample", n_pairs, rows && prm && out, stream, x0, x1, n_img, H, W, nnz, n_nnz, rows, prm,
+	                                                out);
 }
 
 int mc_train_step_batch(const float *patches, int n_pairs, float *params, float *moms, float lr, float mom, float margin, int pow,
                         float *loss_out, void *workspace, size_t workspace_bytes, void *stream)
 {
-	if (int rc = check_step_args<Net>(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
-	MC_REQUIRE(patches && loss_out, "train_step_batch: null pointer");
-	if (int rc = prepare_step_kernels()) return rc;
-	return enqueue_step(patches, nullptr, nullptr, 0, 0, 0, nullptr, 0, nullptr, nullptr, n_pairs, params, moms, lr, mom, margin, pow,
-	                    loss_out, workspace, as_stream(stream));
+	return step_batch<Net, train_step_kernel<false>, train_sgd_kernel>(prepare_step_kernels, patches, n_pairs, params, moms, lr, mom, margin, pow,
+	                                                                    loss_out, workspace, workspace_bytes, stream, nullptr, nullptr, 0, 0, 0,
+	                                                                    nullptr, 0, nullptr, nullptr);
 }
 
 int mc_train_run(const float *x0, const float *x1, int n_img, int H, int W, const float *nnz, int64_t n_nnz, const int32_t *perm,
@@ -142,8 +109,9 @@ int mc_train_run(const float *x0, const float *x1, int n_img, int H, int W, cons
 	if (int rc = check_step_args<Net>(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
 	const hipStream_t st = as_stream(stream);
 	return run_steps(Net::PREFIX, perm && prm && losses, t0, n_steps, n_pairs, n_perm, prepare_step_kernels, [&](int s, int64_t first) {
-		return enqueue_step(nullptr, x0, x1, n_img, H, W, nnz, n_nnz, perm + t0 + first, prm + first * NPRM, n_pairs, params, moms, lr, mom, margin,
-		                    pow, losses + s, workspace, st);
+		return enqueue_step<Net, train_step_kernel<true>, train_sgd_kernel>(n_pairs, params, moms, lr, mom, margin, pow, losses + s, workspace, st,
+		                                                                     nullptr, x0, x1, n_img, H, W, nnz, n_nnz, perm + t0 + first,
+		                                                                     prm + first * NPRM);
 	});
 }
 

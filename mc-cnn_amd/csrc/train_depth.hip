@@ -1,37 +1,31 @@
 // Training of the fast architecture at -l1 1..5 (main.lua:212-214, 240-242, 271-273, 726-746) on gfx950: libmctraindepth.so.
 //
-// The step is train.hip's and train_mb.hip's (train_conv.h states it once over a net of train_net.h): l1 valid 3x3 convolutions of
-// 64 maps on patches of side 2 l1 + 1, one workgroup of eight waves per pair with every activation in LDS, the pair's gradients
-// into its own slab row, then the update that sums the slab in pair order.  A depth is an instantiation: the kernels below are
-// templates of L, each entry point switches on l1 (with_depth), and Net<4> and Net<5> are the constants of libmctrain.so's and
-// libmctrainmb.so's nets, so the three libraries compute the same bits where they overlap.  Both image stores are served: x0 / x1
-// of a KITTI set (train_sampler.h) and Middlebury's ragged planes (train_mb_sampler.h).
+// The step is the fast net's of train_fast.h, which states the net, the kernels' bodies and the host side of a step once for
+// libmctrain.so, libmctrainmb.so and this library: l1 valid 3x3 convolutions of 64 maps on patches of side 2 l1 + 1, one
+// workgroup of eight waves per pair with every activation in LDS, the pair's gradients into its own slab row, then the update
+// that sums the slab in pair order.  A depth is an instantiation: the kernels below are templates of L and each entry point
+// switches on l1 (with_depth); at l1 4 and 5 they instantiate what libmctrain.so and libmctrainmb.so instantiate, so the three
+// libraries compute the same bits where they overlap.  Both image stores are served: x0 / x1 of a KITTI set (train_sampler.h)
+// and Middlebury's ragged planes (train_mb_sampler.h).
 //
 // What a depth changes in the GEMMs (N columns, padded to 32; split_k(N) slices K over four waves where N <= 32):
 //   l1 = 1: one forward GEMM of N = 3 (K = 9 taps in 5 steps, split 1 1 1 2), one weight gradient of K = 3, no data gradient;
 //   l1 = 2: forward N = 27 (the first layer split for once: 5 steps again), 3; data gradient N = 27;
 //   l1 = 3: forward N = 75, 27, 3; data gradient N = 27, 75.
-// Every kernel's dynamic-LDS limit is raised to its own depth's size (prepare<L>), once per depth.
+// Every kernel's dynamic-LDS limit is raised to its own depth's size (train_fast.h's raise_lds_limit), once per depth.
 #include "mc_common.h"
 #include "../../include/mc_train_depth.h"
-#include "train_mb_sampler.h"   // sample_mb_pixel, and train_sampler.h's sample_pair_pixel
-#include "train_conv.h"         // the GEMMs, the step of a net, the update
+#include "train_fast.h"   // the fast net, its kernels' bodies over either store, the host side of a step
 
 namespace mc {
 
-template <int L_>
-struct Net {
-	static constexpr int L = L_;
-	static constexpr int FM = MC_TRAIN_DEPTH_FM, PS = 2 * L + 1, NL = L, NP = 3, L2 = 0, MAX_PAIRS = MC_TRAIN_DEPTH_MAX_PAIRS;
+struct Lib {
 	static constexpr const char *PREFIX = "train_depth";
-	static constexpr int NPIX = 3 * PS * PS;                  // floats of a pair's patches
-	static constexpr int SAMPLE_NT = (NPIX + 63) / 64 * 64;   // the sample kernel's block: a thread per patch pixel, whole waves
-	static constexpr int NPARAMS = n_conv<Net>();
-	static constexpr size_t LDS_BYTES = STEP_LDS_BYTES<Net>;
+	static constexpr int MAX_PAIRS = MC_TRAIN_DEPTH_MAX_PAIRS;
 };
-constexpr int NPRM = MC_TRAIN_DEPTH_NPRM;
+template <int L> using Net = FastNet<L, Lib>;
 constexpr int MIN_L1 = MC_TRAIN_DEPTH_MIN_L1, MAX_L1 = MC_TRAIN_DEPTH_MAX_L1;
-static_assert(NPRM == MC_TRAIN_NPRM && NPRM == MC_TRAIN_MB_NPRM, "the sampler's parameter layout");
+static_assert(Net<1>::FM == MC_TRAIN_DEPTH_FM && NPRM == MC_TRAIN_DEPTH_NPRM, "the net of mc_train_depth.h");
 static_assert(Net<1>::NPARAMS == 640 && Net<2>::NPARAMS == 37568 && Net<3>::NPARAMS == 74496, "640 + (l1 - 1) * 36 928");
 static_assert(Net<4>::NPARAMS == MC_TRAIN_NPARAMS && Net<5>::NPARAMS == MC_TRAIN_MB_NPARAMS, "the layouts of mc_train.h and mc_train_mb.h");
 static_assert(Net<1>::LDS_BYTES == 34048 && Net<2>::LDS_BYTES == 40960 && Net<3>::LDS_BYTES == 60672, "the LDS layout");
@@ -48,10 +42,7 @@ __global__ void __launch_bounds__(Net<L>::SAMPLE_NT) train_depth_sample_kernel(c
                                                                               const int32_t *__restrict__ rows, const float *__restrict__ prm,
                                                                               float *__restrict__ out)
 {
-	constexpr int NPIX = Net<L>::NPIX;
-	const int pair = blockIdx.x, t = threadIdx.x;
-	if (t < NPIX)
-		out[(int64_t)pair * NPIX + t] = sample_pair_pixel<Net<L>::PS>(x0, x1, n_img, H, W, nnz, n_nnz, rows[pair], prm + (int64_t)pair * NPRM, t);
+	write_patches<Net<L>, ImageStore>(out, x0, x1, n_img, H, W, nnz, n_nnz, rows, prm);
 }
 
 // One workgroup per pair.  SAMPLE: the patches come from the images (rows[pair] of nnz, prm of the pair); otherwise from patches
@@ -63,17 +54,7 @@ __global__ void __launch_bounds__(NT) train_depth_step_kernel(const float *__res
                                                               const float *__restrict__ prm, const float *__restrict__ params, float margin,
                                                               int pow, float inv_pairs, float *__restrict__ slab, float *__restrict__ losses)
 {
-	constexpr int NPIX = Net<L>::NPIX;
-	extern __shared__ __attribute__((aligned(16))) float lds[];
-	const int pair = blockIdx.x, t = threadIdx.x;
-	if (t < NPIX) {
-		if (SAMPLE)
-			lds[t] = sample_pair_pixel<Net<L>::PS>(x0, x1, n_img, H, W, nnz, n_nnz, rows[pair], prm + (int64_t)pair * NPRM, t);
-		else
-			lds[t] = patches[(int64_t)pair * NPIX + t];
-	}
-	__syncthreads();
-	pair_step<Net<L>>(params, margin, pow, inv_pairs, lds, slab + (int64_t)pair * Net<L>::NPARAMS, losses + pair);
+	step_of_pair<Net<L>, SAMPLE, ImageStore>(patches, params, margin, pow, inv_pairs, slab, losses, x0, x1, n_img, H, W, nnz, n_nnz, rows, prm);
 }
 
 // ---- the ragged store: planes, table, src ------------------------------------------------------------------------------------
@@ -84,11 +65,7 @@ __global__ void __launch_bounds__(Net<L>::SAMPLE_NT) train_depth_mb_sample_kerne
                                                                                  const int32_t *__restrict__ rows, const int32_t *__restrict__ src,
                                                                                  const float *__restrict__ prm, float *__restrict__ out)
 {
-	constexpr int NPIX = Net<L>::NPIX;
-	const int pair = blockIdx.x, t = threadIdx.x;
-	if (t < NPIX)
-		out[(int64_t)pair * NPIX + t] = sample_mb_pixel<Net<L>::PS>(planes, table, n_planes, nnz, n_nnz, rows[pair], src + 2 * (int64_t)pair,
-		                                                             prm + (int64_t)pair * NPRM, t);
+	write_patches<Net<L>, RaggedStore>(out, planes, table, n_planes, nnz, n_nnz, rows, src, prm);
 }
 
 // The step on the ragged store; it takes given patches only through train_depth_step_kernel<L, false>.
@@ -99,12 +76,7 @@ __global__ void __launch_bounds__(NT) train_depth_mb_step_kernel(const float *__
                                                                  const float *__restrict__ prm, const float *__restrict__ params, float margin,
                                                                  int pow, float inv_pairs, float *__restrict__ slab, float *__restrict__ losses)
 {
-	extern __shared__ __attribute__((aligned(16))) float lds[];
-	const int pair = blockIdx.x, t = threadIdx.x;
-	if (t < Net<L>::NPIX)
-		lds[t] = sample_mb_pixel<Net<L>::PS>(planes, table, n_planes, nnz, n_nnz, rows[pair], src + 2 * (int64_t)pair, prm + (int64_t)pair * NPRM, t);
-	__syncthreads();
-	pair_step<Net<L>>(params, margin, pow, inv_pairs, lds, slab + (int64_t)pair * Net<L>::NPARAMS, losses + pair);
+	step_of_pair<Net<L>, true, RaggedStore>(nullptr, params, margin, pow, inv_pairs, slab, losses, planes, table, n_planes, nnz, n_nnz, rows, src, prm);
 }
 
 // g = sum over pairs in order; v = mom * v - lr * g; w += v.  Block 0 also writes the mean loss.  One kernel for every depth.
@@ -116,22 +88,10 @@ __global__ void __launch_bounds__(256) train_depth_sgd_kernel(const float *__res
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-// Lets depth L's three step kernels take that depth's LDS; once per depth (train_net.h's prepare_kernels remembers one answer per
-// library, which is one depth's).
-template <int L> static int prepare()
+template <class N> static int prepare()
 {
-	static int rc = -1;
-	if (rc >= 0) return rc;
-	for (const void *k : {(const void *)train_depth_step_kernel<L, true>, (const void *)train_depth_step_kernel<L, false>,
-	                      (const void *)train_depth_mb_step_kernel<L>}) {
-		const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Net<L>::LDS_BYTES);
-		if (e != hipSuccess) {
-			set_error("train_depth: hipFuncSetAttribute(l1 %d, %zu bytes of LDS): %s", L, Net<L>::LDS_BYTES, hipGetErrorString(e));
-			return (int)e;
-		}
-	}
-	rc = 0;
-	return rc;
+	return raise_lds_limit<N>({(const void *)train_depth_step_kernel<N::L, true>, (const void *)train_depth_step_kernel<N::L, false>,
+	                           (const void *)train_depth_mb_step_kernel<N::L>});
 }
 
 // f(Net<l1>{}) for l1 in [1, 5]; refuses every other depth
@@ -150,17 +110,6 @@ template <class F> static int with_depth(int l1, F f)
 	else
 		set_error("train_depth: l1 %d outside [%d, %d]", l1, MIN_L1, MAX_L1);
 	return MC_EINVAL;
-}
-
-// after the launch of a step kernel of net N: its check, then the update
-template <class N>
-static int enqueue_update(int n_pairs, float *params, float *moms, float lr, float mom, float *loss_out, void *ws, hipStream_t st)
-{
-	float *slab = (float *)ws;
-	if (int rc = check_launch("train_depth_step")) return rc;
-	train_depth_sgd_kernel<<<cdiv(N::NPARAMS, 256), 256, 0, st>>>(slab, slab + (size_t)n_pairs * N::NPARAMS, n_pairs, N::NPARAMS, params, moms, lr, mom,
-	                                                            loss_out);
-	return check_launch("train_depth_sgd");
 }
 
 }  // namespace mc
@@ -192,15 +141,9 @@ int mc_train_depth_step_batch(int l1, const float *patches, int n_pairs, float *
 {
 	return with_depth(l1, [&](auto n) {
 		using N = decltype(n);
-		if (int rc = check_step_args<N>(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
-		MC_REQUIRE(patches && loss_out, "train_depth_step_batch: null pointer");
-		if (int rc = prepare<N::L>()) return rc;
-		const hipStream_t st = as_stream(stream);
-		float *slab = (float *)workspace;
-		train_depth_step_kernel<N::L, false><<<n_pairs, NT, N::LDS_BYTES, st>>>(patches, nullptr, nullptr, 0, 0, 0, nullptr, 0, nullptr, nullptr, params,
-		                                                                         margin, pow, 1.f / (float)n_pairs, slab,
-		                                                                         slab + (size_t)n_pairs * N::NPARAMS);
-		return enqueue_update<N>(n_pairs, params, moms, lr, mom, loss_out, workspace, st);
+		return step_batch<N, train_depth_step_kernel<N::L, false>, train_depth_sgd_kernel>(prepare<N>, patches, n_pairs, params, moms, lr, mom, margin,
+		                                                                                    pow, loss_out, workspace, workspace_bytes, stream, nullptr,
+		                                                                                    nullptr, 0, 0, 0, nullptr, 0, nullptr, nullptr);
 	});
 }
 
@@ -210,10 +153,8 @@ int mc_train_depth_sample(int l1, const float *x0, const float *x1, int n_img, i
 	return with_depth(l1, [&](auto n) {
 		using N = decltype(n);
 		if (int rc = check_image_args(N::PREFIX, x0, x1, n_img, H, W, nnz, n_nnz)) return rc;
-		MC_REQUIRE(n_pairs >= 1 && n_pairs <= (1 << 24), "train_depth_sample: n_pairs %d", n_pairs);
-		MC_REQUIRE(rows && prm && out, "train_depth_sample: null pointer");
-		train_depth_sample_kernel<N::L><<<n_pairs, N::SAMPLE_NT, 0, as_stream(stream)>>>(x0, x1, n_img, H, W, nnz, n_nnz, rows, prm, out);
-		return check_launch("train_depth_sample");
+		return sample_patches<N, train_depth_sample_kernel<N::L>>("train_depth_sample", n_pairs, rows && prm && out, stream, x0, x1, n_img, H, W, nnz,
+		                                                          n_nnz, rows, prm, out);
 	});
 }
 
@@ -226,12 +167,10 @@ int mc_train_depth_run(int l1, const float *x0, const float *x1, int n_img, int 
 		if (int rc = check_image_args(N::PREFIX, x0, x1, n_img, H, W, nnz, n_nnz)) return rc;
 		if (int rc = check_step_args<N>(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
 		const hipStream_t st = as_stream(stream);
-		float *slab = (float *)workspace;
-		return run_steps(N::PREFIX, perm && prm && losses, t0, n_steps, n_pairs, n_perm, prepare<N::L>, [&](int s, int64_t first) {
-			train_depth_step_kernel<N::L, true><<<n_pairs, NT, N::LDS_BYTES, st>>>(nullptr, x0, x1, n_img, H, W, nnz, n_nnz, perm + t0 + first,
-			                                                                        prm + first * NPRM, params, margin, pow, 1.f / (float)n_pairs, slab,
-			                                                                        slab + (size_t)n_pairs * N::NPARAMS);
-			return enqueue_update<N>(n_pairs, params, moms, lr, mom, losses + s, workspace, st);
+		return run_steps(N::PREFIX, perm && prm && losses, t0, n_steps, n_pairs, n_perm, prepare<N>, [&](int s, int64_t first) {
+			return enqueue_step<N, train_depth_step_kernel<N::L, true>, train_depth_sgd_kernel>(n_pairs, params, moms, lr, mom, margin, pow, losses + s,
+			                                                                                     workspace, st, nullptr, x0, x1, n_img, H, W, nnz, n_nnz,
+			                                                                                     perm + t0 + first, prm + first * NPRM);
 		});
 	});
 }
@@ -242,10 +181,8 @@ int mc_train_depth_mb_sample(int l1, const float *planes, const mc_train_mb_plan
 	return with_depth(l1, [&](auto n) {
 		using N = decltype(n);
 		if (int rc = check_store_args(N::PREFIX, planes, table, n_planes, nnz, n_nnz)) return rc;
-		MC_REQUIRE(n_pairs >= 1 && n_pairs <= (1 << 24), "train_depth_mb_sample: n_pairs %d", n_pairs);
-		MC_REQUIRE(rows && src && prm && out, "train_depth_mb_sample: null pointer");
-		train_depth_mb_sample_kernel<N::L><<<n_pairs, N::SAMPLE_NT, 0, as_stream(stream)>>>(planes, table, n_planes, nnz, n_nnz, rows, src, prm, out);
-		return check_launch("train_depth_mb_sample");
+		return sample_patches<N, train_depth_mb_sample_kernel<N::L>>("train_depth_mb_sample", n_pairs, rows && src && prm && out, stream, planes, table,
+		                                                             n_planes, nnz, n_nnz, rows, src, prm, out);
 	});
 }
 
@@ -259,12 +196,10 @@ int mc_train_depth_mb_run(int l1, const float *planes, const mc_train_mb_plane *
 		if (int rc = check_store_args(N::PREFIX, planes, table, n_planes, nnz, n_nnz)) return rc;
 		if (int rc = check_step_args<N>(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
 		const hipStream_t st = as_stream(stream);
-		float *slab = (float *)workspace;
-		return run_steps(N::PREFIX, perm && src && prm && losses, t0, n_steps, n_pairs, n_perm, prepare<N::L>, [&](int s, int64_t first) {
-			train_depth_mb_step_kernel<N::L><<<n_pairs, NT, N::LDS_BYTES, st>>>(planes, table, n_planes, nnz, n_nnz, perm + t0 + first, src + 2 * first,
-			                                                                     prm + first * NPRM, params, margin, pow, 1.f / (float)n_pairs, slab,
-			                                                                     slab + (size_t)n_pairs * N::NPARAMS);
-			return enqueue_update<N>(n_pairs, params, moms, lr, mom, losses + s, workspace, st);
+		return run_steps(N::PREFIX, perm && src && prm && losses, t0, n_steps, n_pairs, n_perm, prepare<N>, [&](int s, int64_t first) {
+			return enqueue_step<N, train_depth_mb_step_kernel<N::L>, train_depth_sgd_kernel>(n_pairs, params, moms, lr, mom, margin, pow, losses + s,
+			                                                                                  workspace, st, planes, table, n_planes, nnz, n_nnz,
+			                                                                                  perm + t0 + first, src + 2 * first, prm + first * NPRM);
 		});
 	});
 }

@@ -1,6 +1,7 @@
 // Training of the fast architecture on Middlebury (main.lua:602-890, `mb fast`: -l1 5 -fm 64) on gfx950: libmctrainmb.so.
 //
-// The step is train.hip's (train_conv.h states it once for both) with five valid 3x3 convolutions on 11 x 11 patches
+// The step is the fast net's of train_fast.h, which states the net, the kernels' bodies and the host side of a step once for
+// libmctrain.so, this library and libmctraindepth.so, with five valid 3x3 convolutions on 11 x 11 patches
 // (11 -> 9 -> 7 -> 5 -> 3 -> 1) and a ragged image store (include/mc_train_mb.h).  TWO kernels:
 //   (a) train_mb_step_kernel: one workgroup of 8 waves per pair; the pair's three patches are sampled from their planes into
 //       LDS (or copied from given patches), forward, Normalize2 / StereoJoin1 / Margin2, backward with every activation in
@@ -22,35 +23,27 @@
 // K is split over four waves where a GEMM has only two output tiles: forward of layers 4 and 5, data gradient of layer 5.
 #include "mc_common.h"
 #include "../../include/mc_train_mb.h"
-#include "train_mb_sampler.h"   // sample_mb_pixel: a pair's patches from the ragged store, shared with train_mb_slow.hip
-#include "train_conv.h"         // the GEMMs, the step of a net, the update
+#include "train_fast.h"   // the fast net, its kernels' bodies (the sampler is train_mb_sampler.h's), the host side of a step
 
 namespace mc {
 
-struct Net {
-	static constexpr int FM = MC_TRAIN_MB_FM, PS = MC_TRAIN_MB_WS, NL = MC_TRAIN_MB_L1, NP = 3, L2 = 0, MAX_PAIRS = MC_TRAIN_MB_MAX_PAIRS;
+struct Lib {
 	static constexpr const char *PREFIX = "train_mb";
+	static constexpr int MAX_PAIRS = MC_TRAIN_MB_MAX_PAIRS;
 };
-static_assert(MC_TRAIN_MB_NPRM == MC_TRAIN_NPRM, "the sampler's parameter layout");
-constexpr int PS = Net::PS;
-constexpr int NPIX = 3 * PS * PS;        // floats of a pair's patches
-constexpr int NPRM = MC_TRAIN_MB_NPRM;
-constexpr int NPARAMS = MC_TRAIN_MB_NPARAMS;
-static_assert(n_conv<Net>() == NPARAMS && off_b<Net>(Net::NL) + FM == NPARAMS, "parameter layout: w1 b1 w2 b2 ... w5 b5");
+using Net = FastNet<MC_TRAIN_MB_L1, Lib>;
+static_assert(Net::FM == MC_TRAIN_MB_FM && Net::PS == MC_TRAIN_MB_WS && NPRM == MC_TRAIN_MB_NPRM && Net::SAMPLE_NT == 384, "the net of mc_train_mb.h");
+static_assert(Net::NPARAMS == MC_TRAIN_MB_NPARAMS && off_b<Net>(Net::NL) + FM == Net::NPARAMS, "parameter layout: w1 b1 w2 b2 ... w5 b5");
 // LDS: X [3][121] in 384 floats, A1 [3][64][81], A2 [3][64][49], A3 [3][64][25], A4 [3][64][9], A5 [3][64], the partial tiles
-constexpr size_t LDS_BYTES = STEP_LDS_BYTES<Net>;
-static_assert(NPIX <= lds_act<Net>(1) && lds_act<Net>(1) == 384 && NPIX <= NT, "the patches' slot, one thread per patch pixel");
-static_assert(LDS_BYTES == 161024 && LDS_BYTES <= 160 * 1024, "a CU has 160 KiB of LDS");
+static_assert(Net::NPIX <= lds_act<Net>(1) && lds_act<Net>(1) == 384 && Net::NPIX <= NT, "the patches' slot, one thread per patch pixel");
+static_assert(Net::LDS_BYTES == 161024 && Net::LDS_BYTES <= 160 * 1024, "a CU has 160 KiB of LDS");
 
 __global__ void __launch_bounds__(384) train_mb_sample_kernel(const float *__restrict__ planes, const mc_train_mb_plane *__restrict__ table,
                                                               int n_planes, const float *__restrict__ nnz, int64_t n_nnz,
                                                               const int32_t *__restrict__ rows, const int32_t *__restrict__ src,
                                                               const float *__restrict__ prm, float *__restrict__ out)
 {
-	const int pair = blockIdx.x, t = threadIdx.x;
-	if (t < NPIX)
-		out[(int64_t)pair * NPIX + t] = sample_mb_pixel<PS>(planes, table, n_planes, nnz, n_nnz, rows[pair], src + 2 * (int64_t)pair,
-		                                                    prm + (int64_t)pair * NPRM, t);
+	write_patches<Net, RaggedStore>(out, planes, table, n_planes, nnz, n_nnz, rows, src, prm);
 }
 
 // Kernel (a): one workgroup per pair.  SAMPLE: the patches come from the planes (rows[pair] of nnz, src and prm of the
@@ -63,16 +56,7 @@ __global__ void __launch_bounds__(NT) train_mb_step_kernel(const float *__restri
                                                            const float *__restrict__ params, float margin, int pow, float inv_pairs,
                                                            float *__restrict__ slab, float *__restrict__ losses)
 {
-	extern __shared__ __attribute__((aligned(16))) float lds[];
-	const int pair = blockIdx.x, t = threadIdx.x;
-	if (t < NPIX) {
-		if (SAMPLE)
-			lds[t] = sample_mb_pixel<PS>(planes, table, n_planes, nnz, n_nnz, rows[pair], src + 2 * (int64_t)pair, prm + (int64_t)pair * NPRM, t);
-		else
-			lds[t] = patches[(int64_t)pair * NPIX + t];
-	}
-	__syncthreads();
-	pair_step<Net>(params, margin, pow, inv_pairs, lds, slab + (int64_t)pair * NPARAMS, losses + pair);
+	step_of_pair<Net, SAMPLE, RaggedStore>(patches, params, margin, pow, inv_pairs, slab, losses, planes, table, n_planes, nnz, n_nnz, rows, src, prm);
 }
 
 // Kernel (b): g = sum over pairs in order; v = mom * v - lr * g; w += v.  Block 0 also writes the mean loss.
@@ -80,29 +64,12 @@ __global__ void __launch_bounds__(256) train_mb_sgd_kernel(const float *__restri
                                                            float *__restrict__ params, float *__restrict__ moms, float lr, float mom,
                                                            float *__restrict__ loss_out)
 {
-	slab_sgd(slab, pair_losses, n_pairs, NPARAMS, params, moms, lr, mom, loss_out);
+	slab_sgd(slab, pair_losses, n_pairs, Net::NPARAMS, params, moms, lr, mom, loss_out);
 }
 
 static int prepare_step_kernels()
 {
-	return prepare_kernels(Net::PREFIX, {(const void *)train_mb_step_kernel<true>, (const void *)train_mb_step_kernel<false>}, LDS_BYTES);
-}
-
-static int enqueue_step(const float *patches, const float *planes, const mc_train_mb_plane *table, int n_planes, const float *nnz,
-                        int64_t n_nnz, const int32_t *rows, const int32_t *src, const float *prm, int n_pairs, float *params, float *moms,
-                        float lr, float mom, float margin, int pow, float *loss_out, void *ws, hipStream_t st)
-{
-	float *slab = (float *)ws;
-	float *pair_losses = slab + (size_t)n_pairs * NPARAMS;
-	if (patches)
-		train_mb_step_kernel<false><<<n_pairs, NT, LDS_BYTES, st>>>(patches, planes, table, n_planes, nnz, n_nnz, rows, src, prm, params,
-		                                                                  margin, pow, 1.f / (float)n_pairs, slab, pair_losses);
-	else
-		train_mb_step_kernel<true><<<n_pairs, NT, LDS_BYTES, st>>>(patches, planes, table, n_planes, nnz, n_nnz, rows, src, prm, params,
-		                                                                 margin, pow, 1.f / (float)n_pairs, slab, pair_losses);
-	if (int rc = check_launch("train_mb_step")) return rc;
-	train_mb_sgd_kernel<<<cdiv(NPARAMS, 256), 256, 0, st>>>(slab, pair_losses, n_pairs, params, moms, lr, mom, loss_out);
-	return check_launch("train_mb_sgd");
+	return raise_lds_limit<Net>({(const void *)train_mb_step_kernel<true>, (const void *)train_mb_step_kernel<false>});
 }
 
 }  // namespace mc
@@ -124,20 +91,16 @@ int mc_train_mb_sample(const float *planes, const mc_train_mb_plane *table, int 
                        const int32_t *rows, const int32_t *src, const float *prm, int n_pairs, float *out, void *stream)
 {
 	if (int rc = check_store_args(Net::PREFIX, planes, table, n_planes, nnz, n_nnz)) return rc;
-	MC_REQUIRE(n_pairs >= 1 && n_pairs <= (1 << 24), "train_mb_sample: n_pairs %d", n_pairs);
-	MC_REQUIRE(rows && src && prm && out, "train_mb_sample: null pointer");
-	train_mb_sample_kernel<<<n_pairs, 384, 0, as_stream(stream)>>>(planes, table, n_planes, nnz, n_nnz, rows, src, prm, out);
-	return check_launch("train_mb_sample");
+	return sample_patches<Net, train_mb_sample_kernel>("train_mb_sample", n_pairs, rows && src && prm && out, stream, planes, table, n_planes, nnz,
+	                                                   n_nnz, rows, src, prm, out);
 }
 
 int mc_train_mb_step_batch(const float *patches, int n_pairs, float *params, float *moms, float lr, float mom, float margin, int pow,
                            float *loss_out, void *workspace, size_t workspace_bytes, void *stream)
 {
-	if (int rc = check_step_args<Net>(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
-	MC_REQUIRE(patches && loss_out, "train_mb_step_batch: null pointer");
-	if (int rc = prepare_step_kernels()) return rc;
-	return enqueue_step(patches, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, n_pairs, params, moms, lr, mom, margin, pow,
-	                    loss_out, workspace, as_stream(stream));
+	return step_batch<Net, train_mb_step_kernel<false>, train_mb_sgd_kernel>(prepare_step_kernels, patches, n_pairs, params, moms, lr, mom, margin,
+	                                                                          pow, loss_out, workspace, workspace_bytes, stream, nullptr, nullptr, 0,
+	                                                                          nullptr, 0, nullptr, nullptr, nullptr);
 }
 
 int mc_train_mb_run(const float *planes, const mc_train_mb_plane *table, int n_planes, const float *nnz, int64_t n_nnz,
@@ -149,8 +112,9 @@ int mc_train_mb_run(const float *planes, const mc_train_mb_plane *table, int n_p
 	if (int rc = check_step_args<Net>(n_pairs, params, moms, margin, pow, workspace, workspace_bytes)) return rc;
 	const hipStream_t st = as_stream(stream);
 	return run_steps(Net::PREFIX, perm && src && prm && losses, t0, n_steps, n_pairs, n_perm, prepare_step_kernels, [&](int s, int64_t first) {
-		return enqueue_step(nullptr, planes, table, n_planes, nnz, n_nnz, perm + t0 + first, src + 2 * first, prm + first * NPRM, n_pairs, params,
-		                    moms, lr, mom, margin, pow, losses + s, workspace, st);
+		return enqueue_step<Net, train_mb_step_kernel<true>, train_mb_sgd_kernel>(n_pairs, params, moms, lr, mom, margin, pow, losses + s, workspace, st,
+		                                                                           nullptr, planes, table, n_planes, nnz, n_nnz, perm + t0 + first,
+		                                                                           src + 2 * first, prm + first * NPRM);
 	});
 }
 

@@ -1,7 +1,8 @@
 """GPU: the four training libraries give, bit for bit, what they gave before their layer chains, LDS layouts and host code
-were stated once in shared headers.  tests/golden/train_bitwise.json (tests/golden/make_train_bitwise.py) holds SHA-256 of the
+were stated once in shared headers, and libmctraindepth.so at l1 1, 2 and 3 what it gave before the fast net's kernels were
+stated once in csrc/train_fast.h.  tests/golden/train_bitwise.json (tests/golden/make_train_bitwise.py) holds SHA-256 of the
 parameters, the momenta and the losses of the cases of tests/train_golden_cases.py, recorded from the libraries of the
-commit before that change; every arithmetic order is fixed by the source under -ffp-contract=off, so the comparison is of
+commit before each change; every arithmetic order is fixed by the source under -ffp-contract=off, so the comparison is of
 hashes alone and has no tolerance."""
 import json
 import os
@@ -25,7 +26,7 @@ def results():
 
 
 def test_the_cases_are_the_recorded_ones(results):
-    assert set(results) == set(GOLDEN["cases"]) and len(results) == 14
+    assert set(results) == set(GOLDEN["cases"]) and len(results) == 32
     for name, r in results.items():
         assert tg.vacuous(r) is None, (name, tg.vacuous(r))
 

@@ -1,6 +1,8 @@
 """The cases of tests/test_gpu_train_golden.py, shared with tests/golden/make_train_bitwise.py, which records them: small runs
 of the four training libraries whose parameters, momenta and losses are compared bit for bit (as SHA-256 of their bytes)
-with what the libraries gave before their layer chains and host code were stated once.
+with what the libraries gave before their layer chains and host code were stated once, and of libmctraindepth.so at l1 1, 2
+and 3 on both stores (one run with pow 1, one step with pow 2, one sample each) with what it gave before the fast net's
+kernels were stated once in csrc/train_fast.h.
 
 Every case has n_pairs = 9: 18 FC rows are a ragged last 16-row tile, and 9 (27 for libmctrainmbslow.so) slab rows are summed
 in order.  `run` is mc_train*_run with n_steps = 3 from t0 = 5, `step` one mc_train*_step_batch on given patches (the
@@ -126,10 +128,43 @@ def _mb_cases(mod, tm, seed, scalars_list):
     return out
 
 
+def _depth_cases(td, main, tm, l1, store, seed):
+    """libmctraindepth.so at depth l1 on `store` ("kitti" | "mb"): a run with pow 1, a step on given patches with pow 2, the
+    sampler.  The shallow depths have no older library to be compared with (tests/test_gpu_train_depth.py)."""
+    import torch
+    shape = td.net_shape(l1)
+    conv, _ = shape.init_net(seed, gain=GAIN)
+    p0 = shape.flat_params(conv)
+    rng = np.random.default_rng(seed + 1)
+    cuda = torch.device("cuda")
+    losses = torch.empty(N_STEPS, dtype=torch.float32, device="cuda")
+    if store == "kitti":
+        x0, x1, nnz, perm = kitti_set()
+        prm = tm.draw_params(rng, main.parse(["kitti", "fast", "-a", "train_tr", "-hflip", "1"])[2], N_STEPS, N_PAIRS)
+        t = td.Trainer(x0, x1, nnz, perm, conv, N_PAIRS, cuda)
+        t.run(T0, _dev(prm), 0.002, 0.9, MARGIN, 1, losses)
+        got = td.sample(l1, t.x0, t.x1, t.nnz, _dev(perm[T0:T0 + N_PAIRS]), _dev(prm[0]))
+    else:
+        planes, table, index, nnz, perm = mb_set(tm)
+        opt = tm.parse(["mb", "fast", "-a", "train_tr", "-hflip", "1", "-d_exp", "0.5", "-d_light", "0.5"])[2]
+        prm = tm.draw_params(rng, opt, N_STEPS, N_PAIRS)
+        src = tm.draw_sources(rng, opt, nnz[perm[T0:T0 + N_STEPS * N_PAIRS], 0].reshape(N_STEPS, N_PAIRS), index)
+        t = td.MbTrainer(planes, table, nnz, perm, conv, N_PAIRS, cuda)
+        t.run(T0, _dev(src), _dev(prm), 0.002, 0.9, MARGIN, 1, losses)
+        got = td.mb_sample(l1, t.planes, t.table, t.nnz, _dev(perm[T0:T0 + N_PAIRS]), _dev(src[0]), _dev(prm[0]))
+    out = {"run_pow1": _result(shape, p0, t.params, t.moms, losses)}
+    patches = rng.standard_normal((N_PAIRS, 3, 2 * l1 + 1, 2 * l1 + 1)).astype(np.float32)
+    params, moms = _dev(p0), torch.zeros(p0.size, dtype=torch.float32, device="cuda")
+    loss = td.step_batch(l1, _dev(patches), params, moms, 0.002, 0.9, MARGIN, 2)
+    out["step_pow2"] = _result(shape, p0, params, moms, loss)
+    out["sample"] = dict(patches=got.cpu().numpy())
+    return {"l1_%d_%s_%s" % (l1, store, name): r for name, r in out.items()}
+
+
 def run_all():
     """{"<library>/<case>": result}: a result has the flat `params`, `moms` and `losses` after the case (and `params0`, the
     NetShape `shape`), the sampler's has `patches`."""
-    from mc_cnn_amd import main, train, train_mb, train_mb_slow, train_slow
+    from mc_cnn_amd import main, train, train_depth, train_mb, train_mb_slow, train_slow
     fast = [("_pow1", (0.002, 0.9, MARGIN, 1)), ("_pow2", (0.002, 0.9, MARGIN, 2))]
     slow = [("", (0.003, 0.9))]
     out = {}
@@ -138,6 +173,10 @@ def run_all():
                        ("libmctrainmbslow.so", _mb_cases(train_mb_slow, train_mb, 24, slow))):
         for name, r in cases.items():
             out["%s/%s" % (lib, name)] = r
+    for l1 in (1, 2, 3):
+        for store in ("kitti", "mb"):
+            for name, r in _depth_cases(train_depth, main, train_mb, l1, store, 30 + 2 * l1).items():
+                out["libmctraindepth.so/" + name] = r
     return out
 
 

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import train_mb_oracle as mo  # noqa: E402
-from test_gpu_train import write_synthetic_kitti  # noqa: E402
+from train_fixtures import write_synthetic_kitti  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import train_oracle as to  # noqa: E402
+from train_fixtures import dev, rel, small_images, write_synthetic_kitti  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -21,22 +22,6 @@ def tr():
     from mc_cnn_amd import train
     assert torch.cuda.is_available()
     return train
-
-
-def dev(a, dtype=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def flat(layers):
-    from mc_cnn_amd import train
-    return train.flat_params(layers)
-
-
-def random_layers(seed):
-    from mc_cnn_amd import main
-    return main.load_net("random:%d" % seed, "kitti", "fast")
 
 
 def test_sampler_matches_the_warp_restatement(tr):
@@ -78,28 +63,6 @@ def test_sampler_matches_the_warp_restatement(tr):
     assert (got[12, 0, :3] == 0).all() and (got[12, 0, 3:, 2:] != 0).all()   # the top rows straddle the border: 0 there
 
 
-def check_per_tensor(got, want, tol):
-    """Each of w1 b1 .. w4 b4 within tol of its own largest magnitude: no tensor's gradient is partly missing."""
-    from mc_cnn_amd import train
-    o = 0
-    for i, (w, b) in enumerate(train.unflat_params(np.zeros(train.tl.NPARAMS, np.float32))):
-        for name, n in (("w%d" % (i + 1), w.size), ("b%d" % (i + 1), b.size)):
-            g, x = got[o:o + n], want[o:o + n]
-            err = np.abs(g - x).max() / np.abs(x).max()
-            print("%s: max error %.2e of its largest magnitude %.2e" % (name, err, np.abs(x).max()))
-            assert err <= tol, name
-            o += n
-
-
-def rel(g, w):
-    return float(np.linalg.norm(g - w) / np.linalg.norm(w))
-
-
-def unflat(v):
-    from mc_cnn_amd import train
-    return train.unflat_params(v)
-
-
 def oracle_patches(rng, n_pairs, scale=1.0):
     return (rng.standard_normal((n_pairs, 3, 9, 9)) * scale).astype(np.float32)
 
@@ -108,10 +71,10 @@ def oracle_patches(rng, n_pairs, scale=1.0):
 def test_step_matches_float64_autograd(tr, pow_):
     import torch
     rng = np.random.default_rng(100 + pow_)
-    layers = random_layers(5)
+    layers = to.random_layers(5)
     n_pairs, lr, mom, margin = 16, 0.002, 0.9, 0.2
     batches = [oracle_patches(rng, n_pairs) for _ in range(20)]
-    params = dev(flat(layers))
+    params = dev(to.flat(layers))
     moms = torch.zeros_like(params)
     ws = torch.empty(tr.tl.load().mc_train_workspace_bytes(n_pairs) // 4 + 1, dtype=torch.float32, device="cuda")
     losses, worst = [], 0.0
@@ -119,13 +82,13 @@ def test_step_matches_float64_autograd(tr, pow_):
         p0, v0 = params.cpu().numpy(), moms.cpu().numpy()
         losses.append(float(tr.step_batch(dev(b), params, moms, lr, mom, margin, pow_, ws).cpu()))
         # every step of the run against float64 autograd from the same (fp32) state
-        wp, wv, wl = to.sgd_steps(unflat(p0), [b], lr, mom, margin, pow_, moms=v0)
+        wp, wv, wl = to.sgd_steps(to.unflat(p0), [b], lr, mom, margin, pow_, moms=v0)
         assert abs(losses[-1] - wl[0]) <= 1e-5, (k, losses[-1], wl[0])
         np.testing.assert_allclose(params.cpu().numpy(), wp, rtol=0, atol=1e-5)
         np.testing.assert_allclose(moms.cpu().numpy(), wv, rtol=0, atol=1e-5)
         if k == 0:
             assert np.abs(wv).max() > 1e-6   # the step moved something
-            check_per_tensor(moms.cpu().numpy(), wv, 1e-4)
+            to.check_per_tensor(moms.cpu().numpy(), wv, 1e-4)
         worst = max(worst, rel(moms.cpu().numpy(), wv))
     # Every step agrees to 1e-5 abs; relative to the small momenta a step can still differ by up to ~4e-3 (measured): where
     # fp32 rounding puts a pre-activation on the other side of 0, a ReLU mask flips and the gradient jumps (a
@@ -144,7 +107,7 @@ def test_step_with_inactive_hinges(tr):
     """A batch where some pairs' hinges are inactive (f <= 0): they contribute no gradient."""
     import torch
     rng = np.random.default_rng(7)
-    layers = random_layers(9)
+    layers = to.random_layers(9)
     n_pairs = 32
     b = oracle_patches(rng, n_pairs)
     b[: n_pairs // 2, 1] = b[: n_pairs // 2, 0]          # positive = left: score 1, hinge inactive
@@ -154,24 +117,14 @@ def test_step_with_inactive_hinges(tr):
     for i in range(n_pairs):
         f.append(float(to.loss_of(wt, xt[i:i + 1], 0.2, 1)))
     assert sum(v == 0 for v in f) >= 4 and sum(v > 0 for v in f) >= 4
-    params = dev(flat(layers))
+    params = dev(to.flat(layers))
     moms = torch.zeros_like(params)
     loss = float(tr.step_batch(dev(b), params, moms, 0.002, 0.9, 0.2, 1).cpu())
     wp, wv, wl = to.sgd_steps(layers, [b], 0.002, 0.9, 0.2, 1)
     assert abs(loss - wl[0]) <= 1e-5
     np.testing.assert_allclose(moms.cpu().numpy(), wv, rtol=0, atol=1e-5)
     np.testing.assert_allclose(params.cpu().numpy(), wp, rtol=0, atol=1e-5)
-    check_per_tensor(moms.cpu().numpy(), wv, 1e-4)
-
-
-def small_images(seed, n_img=3, H=40, W=90):
-    rng = np.random.default_rng(seed)
-    x0 = rng.standard_normal((n_img, H, W)).astype(np.float32)
-    x1 = np.roll(x0, -5, axis=2) + 0.1 * rng.standard_normal((n_img, H, W)).astype(np.float32)
-    ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    nnz = np.stack([np.repeat(np.arange(1, n_img + 1), H * W), np.tile(ys.ravel(), n_img), np.tile(xs.ravel(), n_img),
-                    np.full(n_img * H * W, 5)], 1).astype(np.float32)
-    return x0, x1, nnz
+    to.check_per_tensor(moms.cpu().numpy(), wv, 1e-4)
 
 
 def run_steps(tr, seed, n_steps, n_pairs=64):
@@ -182,7 +135,7 @@ def run_steps(tr, seed, n_steps, n_pairs=64):
     perm = rng.permutation(nnz.shape[0]).astype(np.int32)
     _, _, opt, _ = main.parse(["kitti", "fast", "-a", "train_tr", "-hflip", "1"])
     prm = dev(tr.draw_params(rng, opt, n_steps, n_pairs))
-    t = tr.Trainer(x0, x1, nnz, perm, random_layers(seed), n_pairs, torch.device("cuda"))
+    t = tr.Trainer(x0, x1, nnz, perm, to.random_layers(seed), n_pairs, torch.device("cuda"))
     losses = torch.empty(n_steps, dtype=torch.float32, device="cuda")
     t.run(0, prm, 0.002, 0.9, 0.2, 1, losses)
     torch.cuda.synchronize()
@@ -194,7 +147,7 @@ def test_sampled_step_equals_the_step_on_the_samplers_output(tr):
     t, prm, perm, losses = run_steps(tr, 3, 1)
     x0, x1, nnz = small_images(1)
     patches = tr.sample(dev(x0), dev(x1), dev(nnz), dev(perm[:64]), prm[0])
-    params = dev(flat(random_layers(3)))
+    params = dev(to.flat(to.random_layers(3)))
     moms = torch.zeros_like(params)
     loss = tr.step_batch(patches, params, moms, 0.002, 0.9, 0.2, 1).cpu().numpy()
     assert loss[0] == losses[0]
@@ -211,47 +164,6 @@ def test_runs_are_bitwise_reproducible(tr):
 
 
 # ---- end to end: main.py kitti fast -a train_tr on a synthetic dataset in the data.kitti format ----------------------------
-def write_synthetic_kitti(d, n_img=6, H=48, W=160, seed=0, noise=2.0):
-    """Textured scenes with known piecewise-constant disparity: x1 is x0 shifted by d(y, x) (bands of rows at
-    different depths); dispnoc is d where the match lies inside the image, else 0.  nnz_tr / nnz_te list every known
-    pixel of the training / test images (make_dataset2, adcensus.cu:1900-1929).  x1 carries independent noise of
-    `noise` times the texture's std, so that matching is not trivial for an untrained net."""
-    from mc_cnn_amd import binio
-    os.makedirs(d, exist_ok=True)
-    rng = np.random.default_rng(seed)
-    x0 = np.zeros((n_img, 1, H, W), np.float32)
-    x1 = np.zeros_like(x0)
-    disp = np.zeros_like(x0)
-    k = np.ones(3) / 3
-    for i in range(n_img):
-        r = rng.standard_normal((H, W + 40))
-        r = np.apply_along_axis(lambda v: np.convolve(v, k, "same"), 1, r)
-        r = np.apply_along_axis(lambda v: np.convolve(v, k, "same"), 0, r)
-        r = (r - r.mean()) / r.std()
-        bands = rng.integers(6, 30, 3)
-        d_map = np.repeat(bands, -(-H // 3))[:H][:, None] * np.ones((1, W), np.int64)
-        right = r[:, 40:]
-        left = np.take_along_axis(r, 40 + np.arange(W)[None, :] - d_map, 1)
-        x0[i, 0], x1[i, 0] = left, right + noise * rng.standard_normal(right.shape)
-        disp[i, 0] = np.where(np.arange(W)[None, :] - d_map >= 0, d_map, 0)
-    tr_ids, te_ids = np.arange(1, n_img - 1), np.array([n_img - 1, n_img])
-
-    def nnz_of(ids):
-        rows = []
-        for i in ids:
-            ys, xs = np.nonzero(disp[i - 1, 0] > 0.5)
-            rows.append(np.stack([np.full(ys.size, i), ys, xs, disp[i - 1, 0, ys, xs]], 1))
-        return np.concatenate(rows).astype(np.float32)
-    binio.tofile(os.path.join(d, "x0.bin"), x0)
-    binio.tofile(os.path.join(d, "x1.bin"), x1)
-    binio.tofile(os.path.join(d, "dispnoc.bin"), disp)
-    binio.tofile(os.path.join(d, "metadata.bin"), np.array([[H, W, i] for i in range(n_img)], np.int32))
-    binio.tofile(os.path.join(d, "tr.bin"), tr_ids.astype(np.int32))
-    binio.tofile(os.path.join(d, "te.bin"), te_ids.astype(np.int32))
-    binio.tofile(os.path.join(d, "nnz_tr.bin"), nnz_of(tr_ids))
-    binio.tofile(os.path.join(d, "nnz_te.bin"), nnz_of(te_ids))
-
-
 def test_train_tr_end_to_end(tmp_path, monkeypatch, capsys, tr):
     from mc_cnn_amd import main, t7
     monkeypatch.chdir(tmp_path)

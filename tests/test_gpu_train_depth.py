@@ -17,7 +17,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import train_depth_oracle as do  # noqa: E402
+import train_fast_oracle as do  # noqa: E402
+from train_fixtures import bits, dev, rel, same_bits, small_images, write_synthetic_kitti  # noqa: E402
 from train_mb_oracle import write_synthetic_mb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -30,26 +31,6 @@ def td():
     from mc_cnn_amd import train_depth
     assert torch.cuda.is_available()
     return train_depth
-
-
-def dev(a, dtype=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def bits(t):
-    import torch
-    return t.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    import torch
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def rel(g, w):
-    return float(np.linalg.norm(g - w) / np.linalg.norm(w))
 
 
 def patches_of(rng, n, l1):
@@ -67,17 +48,6 @@ def mb_opt(*extra):
 
 
 # ---- the two stores ---------------------------------------------------------------------------------------------------------------
-def small_images(seed, n_img=3, H=40, W=90):
-    """test_gpu_train.small_images: a KITTI store whose nnz lists every pixel, corners included, at disparity 5."""
-    rng = np.random.default_rng(seed)
-    x0 = rng.standard_normal((n_img, H, W)).astype(np.float32)
-    x1 = np.roll(x0, -5, axis=2) + 0.1 * rng.standard_normal((n_img, H, W)).astype(np.float32)
-    ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    nnz = np.stack([np.repeat(np.arange(1, n_img + 1), H * W), np.tile(ys.ravel(), n_img), np.tile(xs.ravel(), n_img),
-                    np.full(n_img * H * W, 5)], 1).astype(np.float32)
-    return x0, x1, nnz
-
-
 RAGGED = ((23, 37, 2, 2), (4, 4, 1, 1))     # (H, W, lights >= 2, exposures) of two images; 4 x 4 is smaller than every patch but 3 x 3
 
 
@@ -395,41 +365,6 @@ def test_depths_keep_their_own_lds_limit_in_one_process(td):
 
 
 # ---- 6. end to end ---------------------------------------------------------------------------------------------------------------------
-def write_synthetic_kitti(d, n_img=6, H=48, W=160, seed=0, noise=2.0):
-    """test_gpu_train.write_synthetic_kitti: textured scenes with piecewise-constant disparity in the data.kitti format; the
-    last two images are the test set."""
-    from mc_cnn_amd import binio
-    os.makedirs(d, exist_ok=True)
-    rng = np.random.default_rng(seed)
-    x0 = np.zeros((n_img, 1, H, W), np.float32)
-    x1 = np.zeros_like(x0)
-    disp = np.zeros_like(x0)
-    k = np.ones(3) / 3
-    for i in range(n_img):
-        r = rng.standard_normal((H, W + 40))
-        r = np.apply_along_axis(lambda v: np.convolve(v, k, "same"), 1, r)
-        r = np.apply_along_axis(lambda v: np.convolve(v, k, "same"), 0, r)
-        r = (r - r.mean()) / r.std()
-        bands = rng.integers(6, 30, 3)
-        d_map = np.repeat(bands, -(-H // 3))[:H][:, None] * np.ones((1, W), np.int64)
-        right = r[:, 40:]
-        left = np.take_along_axis(r, 40 + np.arange(W)[None, :] - d_map, 1)
-        x0[i, 0], x1[i, 0] = left, right + noise * rng.standard_normal(right.shape)
-        disp[i, 0] = np.where(np.arange(W)[None, :] - d_map >= 0, d_map, 0)
-    tr_ids, te_ids = np.arange(1, n_img - 1), np.array([n_img - 1, n_img])
-
-    def nnz_of(ids):
-        rows = []
-        for i in ids:
-            ys, xs = np.nonzero(disp[i - 1, 0] > 0.5)
-            rows.append(np.stack([np.full(ys.size, i), ys, xs, disp[i - 1, 0, ys, xs]], 1))
-        return np.concatenate(rows).astype(np.float32)
-    for name, a in (("x0", x0), ("x1", x1), ("dispnoc", disp), ("metadata", np.array([[H, W, i] for i in range(n_img)], np.int32)),
-                    ("tr", tr_ids.astype(np.int32)), ("te", te_ids.astype(np.int32)), ("nnz_tr", nnz_of(tr_ids)), ("nnz_te", nnz_of(te_ids))):
-        binio.tofile(os.path.join(d, name + ".bin"), a)
-    return x0, x1
-
-
 def write_png_pair(left, right):
     from PIL import Image
     for name, a in (("l.png", left), ("r.png", right)):

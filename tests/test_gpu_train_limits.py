@@ -6,6 +6,7 @@ the oracle's tail (Normalize2, StereoJoin1, Margin2) against the reference's own
 Per-tensor gradient checks at every step need pairs on which fp32 and float64 agree about every ReLU mask: pairs with a
 pre-activation (or hinge argument) within 3e-6 of 0 in the FLOAT64 forward pass are left out before the GPU is touched
 (`select`); the kernel's output never takes part in the selection."""
+import functools
 import math
 import os
 import sys
@@ -18,6 +19,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import train_oracle as to  # noqa: E402
+import train_fixtures  # noqa: E402
+from train_fixtures import bits, dev, same_bits  # noqa: E402
+
+small_images = functools.partial(train_fixtures.small_images, noise=1.5)   # strong enough to leave most hinges of a random net active
 
 pytestmark = pytest.mark.gpu
 
@@ -35,41 +40,9 @@ def tr():
     return train
 
 
-def dev(a, dtype=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def flat(layers):
-    from mc_cnn_amd import train
-    return train.flat_params(layers)
-
-
-def unflat(v):
-    from mc_cnn_amd import train
-    return train.unflat_params(v)
-
-
-def random_layers(seed):
-    from mc_cnn_amd import main
-    return main.load_net("random:%d" % seed, "kitti", "fast")
-
-
 def opt_of(*flags):
     from mc_cnn_amd import main
     return main.parse(["kitti", "fast", "-a", "train_tr"] + list(flags))[2]
-
-
-def small_images(seed, n_img=3, H=40, W=90, d=5, noise=1.5):
-    """The right view is the left one shifted by d plus noise strong enough to leave most hinges of a random net active."""
-    rng = np.random.default_rng(seed)
-    x0 = rng.standard_normal((n_img, H, W)).astype(np.float32)
-    x1 = np.roll(x0, -d, axis=2) + noise * rng.standard_normal((n_img, H, W)).astype(np.float32)
-    ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    nnz = np.stack([np.repeat(np.arange(1, n_img + 1), H * W), np.tile(ys.ravel(), n_img), np.tile(xs.ravel(), n_img),
-                    np.full(n_img * H * W, d)], 1).astype(np.float32)
-    return x0, x1, nnz
 
 
 def poisoned_workspace(tr, n_pairs):
@@ -78,16 +51,6 @@ def poisoned_workspace(tr, n_pairs):
     need = tr.tl.load().mc_train_workspace_bytes(n_pairs)
     assert need == (n_pairs * tr.tl.NPARAMS + n_pairs) * 4
     return torch.full((need // 4,), NAN, dtype=torch.float32, device="cuda")
-
-
-def bits(t):
-    import torch
-    return t.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    import torch
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 # ---- (a) mc_train_run is the chain sample -> step_batch at every step, for any offset ------------------------------------
@@ -108,7 +71,7 @@ def test_run_equals_the_chain_of_sample_and_step(tr, n_pairs):
     perm = rng.permutation(nnz.shape[0]).astype(np.int32)
     prm = dev(tr.draw_params(rng, opt_of("-hflip", "1", "-vflip", "1", "-d_vtrans", "1", "-d_hshear", "0.2"), n_steps, n_pairs))
     assert (prm[..., 2] < 0).any() and (prm[..., 3] < 0).any()
-    layers = random_layers(8)
+    layers = to.random_layers(8)
     t = tr.Trainer(x0, x1, nnz, perm, layers, n_pairs, torch.device("cuda"))
     t.ws = poisoned_workspace(tr, n_pairs)
     losses = torch.full((n_steps + 1,), -123.25, dtype=torch.float32, device="cuda")
@@ -116,7 +79,7 @@ def test_run_equals_the_chain_of_sample_and_step(tr, n_pairs):
     torch.cuda.synchronize()
     # the chain, with tensors of its own
     x0d, x1d, nnzd, permd = dev(x0), dev(x1), dev(nnz), dev(perm)
-    params, moms = dev(flat(layers)), torch.zeros(tr.tl.NPARAMS, device="cuda")
+    params, moms = dev(to.flat(layers)), torch.zeros(tr.tl.NPARAMS, device="cuda")
     want = []
     for s in range(n_steps):
         rows = permd[t0 + s * n_pairs: t0 + (s + 1) * n_pairs].contiguous()
@@ -144,7 +107,7 @@ def test_run_takes_the_last_legal_offset_and_refuses_one_more(tr):
     n_pairs, n_steps = 3, 2
     n_perm = 17
     perm = np.random.default_rng(0).permutation(nnz.shape[0]).astype(np.int32)[:n_perm]
-    t = tr.Trainer(x0, x1, nnz, perm, random_layers(8), n_pairs, torch.device("cuda"))
+    t = tr.Trainer(x0, x1, nnz, perm, to.random_layers(8), n_pairs, torch.device("cuda"))
     prm = dev(tr.draw_params(np.random.default_rng(1), opt_of(), n_steps, n_pairs))
     losses = torch.full((n_steps,), NAN, dtype=torch.float32, device="cuda")
     t0 = n_perm - n_steps * n_pairs
@@ -152,7 +115,7 @@ def test_run_takes_the_last_legal_offset_and_refuses_one_more(tr):
     torch.cuda.synchronize()
     assert torch.isfinite(losses).all() and torch.isfinite(t.params).all()
     # the same steps through the chain: rows perm[11:14], perm[14:17]
-    params, moms = dev(flat(random_layers(8))), torch.zeros(tr.tl.NPARAMS, device="cuda")
+    params, moms = dev(to.flat(to.random_layers(8))), torch.zeros(tr.tl.NPARAMS, device="cuda")
     for s in range(n_steps):
         rows = t.perm[t0 + s * n_pairs: t0 + (s + 1) * n_pairs].contiguous()
         loss = tr.step_batch(tr.sample(t.x0, t.x1, t.nnz, rows, prm[s].contiguous()), params, moms, 0.002, 0.9, 0.2, 1)
@@ -188,13 +151,13 @@ def pool_size(n):
 def plan_steps(draw, layers, n_pairs, n_steps, lr, mom, margin, pow_, what, moms=None):
     """Batches for n_steps consecutive steps, each selected against the float64 oracle's own trajectory (fp32 state):
     no GPU involved.  draw(m) -> (m, 3, 9, 9) float32 candidates."""
-    p = flat(layers)
+    p = to.flat(layers)
     v = np.zeros_like(p) if moms is None else np.asarray(moms, np.float32)
     batches = []
     for k in range(n_steps):
-        b, _, _ = select(draw(pool_size(n_pairs)), unflat(p), n_pairs, margin, "%s step %d" % (what, k))
+        b, _, _ = select(draw(pool_size(n_pairs)), to.unflat(p), n_pairs, margin, "%s step %d" % (what, k))
         batches.append(b)
-        p, v, _ = to.sgd_steps(unflat(p), [b], lr, mom, margin, pow_, fp32_state=True, moms=v)
+        p, v, _ = to.sgd_steps(to.unflat(p), [b], lr, mom, margin, pow_, fp32_state=True, moms=v)
         p, v = p.astype(np.float32), v.astype(np.float32)
     return batches
 
@@ -205,7 +168,7 @@ def check_step(params, moms, ws, loss, p0, v0, b, lr, mom, margin, pow_, what):
     the NaN-filled workspace included, finite."""
     import torch
     gp, gv = params.cpu().numpy(), moms.cpu().numpy()
-    wp, wv, wl = to.sgd_steps(unflat(p0), [b], lr, mom, margin, pow_, moms=v0)
+    wp, wv, wl = to.sgd_steps(to.unflat(p0), [b], lr, mom, margin, pow_, moms=v0)
     print("%s: loss %.7f (float64 %.7f), max |params - float64| %.2e, max |momenta - float64| %.2e" % (
         what, loss, wl[0], np.abs(gp - wp).max(), np.abs(gv - wv).max()))
     assert math.isfinite(loss) and np.isfinite(gp).all() and np.isfinite(gv).all(), what
@@ -220,7 +183,7 @@ def run_checked_steps(tr, layers, batches, lr, mom, margin, pow_, what):
     """Every batch through mc_train_step_batch on a NaN-filled workspace of exactly the documented size, each step checked
     by check_step."""
     import torch
-    params = dev(flat(layers))
+    params = dev(to.flat(layers))
     moms = torch.zeros_like(params)
     ws = poisoned_workspace(tr, batches[0].shape[0])
     for k, b in enumerate(batches):
@@ -239,7 +202,7 @@ def normal_patches(rng):
 @pytest.mark.parametrize("n_pairs", [1, 2, 3, 65, 257])
 def test_batch_sizes_match_autograd_per_tensor_at_every_step(tr, n_pairs, pow_):
     rng = np.random.default_rng(1000 * pow_ + n_pairs)
-    layers = random_layers(5)
+    layers = to.random_layers(5)
     what = "%d pairs, pow %d" % (n_pairs, pow_)
     batches = plan_steps(normal_patches(rng), layers, n_pairs, 3, 0.002, 0.9, 0.2, pow_, what)
     run_checked_steps(tr, layers, batches, 0.002, 0.9, 0.2, pow_, what)
@@ -254,10 +217,10 @@ def test_gradients_are_summed_in_pair_order(tr, N, pow_):
     import torch
     assert N & (N - 1) == 0
     rng = np.random.default_rng(N + pow_)
-    layers = random_layers(21)
+    layers = to.random_layers(21)
     b = rng.standard_normal((N, 3, 9, 9)).astype(np.float32)
     bd = dev(b)
-    fresh = dev(flat(layers))
+    fresh = dev(to.flat(layers))
     NP = tr.tl.NPARAMS
     G = torch.empty((N, NP), dtype=torch.float32, device="cuda")
     params, moms, ws1 = fresh.clone(), torch.zeros(NP, device="cuda"), poisoned_workspace(tr, 1)
@@ -315,7 +278,7 @@ def test_inactive_hinges_leave_only_the_momentum(tr, pow_):
     the float64 forward pass): every hinge is inactive, the gradient is exactly 0, so v = fl(mom * v), w = fl(w + v)."""
     import torch
     rng = np.random.default_rng(70 + pow_)
-    layers = random_layers(9)
+    layers = to.random_layers(9)
     n_pairs, mom = 32, 0.9
     pool = rng.standard_normal((256, 3, 9, 9)).astype(np.float32)
     pool[:, 1] = pool[:, 0]
@@ -324,7 +287,7 @@ def test_inactive_hinges_leave_only_the_momentum(tr, pow_):
     print("pow %d: %d of %d candidates have f < -1e-3 (f in [%.3f, %.3f])" % (pow_, int((f < -1e-3).sum()), f.size, f.min(), f.max()))
     assert keep.size == n_pairs
     b = pool[keep]
-    params = dev(flat(layers))
+    params = dev(to.flat(layers))
     moms = dev((rng.standard_normal(tr.tl.NPARAMS) * 1e-3).astype(np.float32))
     p0, v0 = params.clone(), moms.clone()
     ws = poisoned_workspace(tr, n_pairs)
@@ -343,7 +306,7 @@ def test_states_whose_gradient_vanishes(tr, case, pow_):
     0 in exact arithmetic (float64 autograd leaves its own rounding, up to 1.3e-17 measured)."""
     import torch
     rng = np.random.default_rng(80)
-    layers = random_layers(10)
+    layers = to.random_layers(10)
     n_pairs = 16
     b = rng.standard_normal((n_pairs, 3, 9, 9)).astype(np.float32)
     if case == "zero_patches":
@@ -357,7 +320,7 @@ def test_states_whose_gradient_vanishes(tr, case, pow_):
     # float64 itself: the loss is the margin's, and what autograd leaves of the gradient is float64 rounding of O(1) terms
     print("%s pow %d: float64 loss %.17g, largest float64 gradient %.2e" % (case, pow_, wl[0], np.abs(wv).max() / 0.002))
     assert abs(wl[0] - want_loss) <= 1e-15 and np.abs(wv).max() <= 0.002 * 1e-14
-    params = dev(flat(layers))
+    params = dev(to.flat(layers))
     moms = torch.zeros_like(params)
     ws = poisoned_workspace(tr, n_pairs)
     loss = float(tr.step_batch(dev(b), params, moms, 0.002, 0.9, 0.2, pow_, ws).cpu())
@@ -371,7 +334,7 @@ def test_states_whose_gradient_vanishes(tr, case, pow_):
 @pytest.mark.parametrize("margin", [0.0, -0.5, 5.0])
 def test_margins_match_autograd(tr, margin):
     rng = np.random.default_rng(90)
-    layers = random_layers(11)
+    layers = to.random_layers(11)
     for pow_ in (1, 2):
         what = "margin %g, pow %d" % (margin, pow_)
         batches = plan_steps(normal_patches(rng), layers, 24, 3, 0.002, 0.9, margin, pow_, what)
@@ -401,7 +364,7 @@ def plan_trained_state(draw_params, n_pairs, n_steps, lr, mom, margin):
     and the right view 2 or 3 columns off the match -- then, from that state, n_steps batches of pairs for the sampler,
     selected against the oracle's own trajectory on the restatement's patches."""
     rng = np.random.default_rng(123)
-    layers = random_layers(12)
+    layers = to.random_layers(12)
     x0, x1, nnz = textured_images(5, noise=NOISE)
     d = 5
 
@@ -427,12 +390,12 @@ def plan_trained_state(draw_params, n_pairs, n_steps, lr, mom, margin):
     for k in range(n_steps):
         rows = cand[k * m:(k + 1) * m]
         pool = np.stack([to.sample_pair(x0, x1, nnz[r], prm_all[k, i]) for i, r in enumerate(rows)])
-        b, f, keep = select(pool, unflat(p), n_pairs, margin, "trained state, step %d" % k)
+        b, f, keep = select(pool, to.unflat(p), n_pairs, margin, "trained state, step %d" % k)
         inactive += int((f <= 0).sum())
         perm.append(rows[keep])
         prm.append(prm_all[k, keep])
         batches.append(b)
-        p, v, _ = to.sgd_steps(unflat(p), [b], lr, mom, margin, 1, fp32_state=True, moms=v)
+        p, v, _ = to.sgd_steps(to.unflat(p), [b], lr, mom, margin, 1, fp32_state=True, moms=v)
         p, v = p.astype(np.float32), v.astype(np.float32)
     share = inactive / float(n_steps * n_pairs)
     print("trained state: %.1f %% of the chosen pairs' hinges are inactive" % (100 * share))
@@ -446,7 +409,7 @@ def test_a_trained_state_on_sampled_patches(tr):
     import torch
     n_pairs, n_steps, lr, mom, margin = 32, 3, 0.002, 0.9, 0.2
     (x0, x1, nnz), (p_tr, v_tr), perm, prm, batches = plan_trained_state(tr.draw_params, n_pairs, n_steps, lr, mom, margin)
-    t = tr.Trainer(x0, x1, nnz, perm, unflat(p_tr), n_pairs, torch.device("cuda"))
+    t = tr.Trainer(x0, x1, nnz, perm, to.unflat(p_tr), n_pairs, torch.device("cuda"))
     t.moms.copy_(dev(v_tr))
     t.ws = poisoned_workspace(tr, n_pairs)
     prm_d = dev(prm)
@@ -683,7 +646,7 @@ def test_the_refusal_baseline_is_accepted(tr, refusal_buffers):
     lib = tr.tl.load()
     tensors, scalars = refusal_buffers
     copies = {k: v.clone() for k, v in tensors.items()}
-    copies["params"] = dev(flat(random_layers(1)))
+    copies["params"] = dev(to.flat(to.random_layers(1)))
     copies["moms"].zero_()
     copies["disp"] = dev(np.random.default_rng(1).uniform(0, 8, (2, 4, 16)).astype(np.float32))
     vals = dict(scalars)

@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import train_mb_oracle as mo  # noqa: E402
+from train_fixtures import dev, rel, same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,21 +24,6 @@ def tm():
     from mc_cnn_amd import train_mb
     assert torch.cuda.is_available()
     return train_mb
-
-
-def dev(a, dtype=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def same_bits(a, b):
-    import torch
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
-def rel(g, w):
-    return float(np.linalg.norm(g - w) / np.linalg.norm(w))
 
 
 def opt_of(*extra):

@@ -20,7 +20,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import train_mb_oracle as mo  # noqa: E402
 from test_gpu_train_mb import candidates, make_store, opt_of  # noqa: E402
-from test_gpu_train_slow_limits import LOSS_SENTINEL, MC_EINVAL, NAN, Guarded, bits, dev, same_bits  # noqa: E402
+from test_gpu_train_slow_limits import LOSS_SENTINEL, MC_EINVAL, NAN, Guarded  # noqa: E402
+from train_fixtures import bits, dev, same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

@@ -22,6 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import train_mb_oracle as mo  # noqa: E402
 import train_mb_slow_oracle as so  # noqa: E402
+from train_fixtures import dev, rel, same_bits  # noqa: E402
 from test_gpu_train_mb import small_set  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -40,21 +41,6 @@ def tms():
 @pytest.fixture(scope="module")
 def wide():
     return so.wide_nets(1)
-
-
-def dev(a, dtype=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def same_bits(a, b):
-    import torch
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
-def rel(g, w):
-    return float(np.linalg.norm(g - w) / np.linalg.norm(w))
 
 
 def sturdy_pairs(conv, fc, seed, n_pairs):

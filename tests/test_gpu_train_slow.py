@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import train_slow_oracle as so  # noqa: E402
-from test_gpu_train import small_images, write_synthetic_kitti  # noqa: E402
+from train_fixtures import dev, rel, small_images, write_synthetic_kitti  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -34,16 +34,6 @@ def ts():
 @pytest.fixture(scope="module")
 def wide():
     return so.wide_nets(1)
-
-
-def dev(a, dtype=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def rel(g, w):
-    return float(np.linalg.norm(g - w) / np.linalg.norm(w))
 
 
 def sturdy_pairs(conv, fc, seed, n_pairs):

@@ -28,8 +28,8 @@ import train_mb_slow_oracle as mso  # noqa: E402
 import train_slow_oracle as so  # noqa: E402
 import test_gpu_train_mb_slow as base_mb_slow  # noqa: E402
 import test_gpu_train_slow as base_slow  # noqa: E402
-from test_gpu_train import small_images  # noqa: E402
 from test_gpu_train_mb import small_set  # noqa: E402
+from train_fixtures import bits, dev, same_bits, small_images  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -39,22 +39,6 @@ MC_EINVAL = -22
 GUARD = 4096                   # sentinel words on either side of a workspace
 SENTINEL = 0x4B1D5EED          # their bit pattern (a finite float, 1.03e7: a kernel that read it would not turn it into NaN)
 LOSS_SENTINEL = -123.25
-
-
-def dev(a, dtype=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def bits(t):
-    import torch
-    return t.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    import torch
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 class Guarded:

@@ -12,7 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import train_depth_oracle as do  # noqa: E402
+import train_fast_oracle as do  # noqa: E402
 from mc_cnn_amd import _train_depth_lib as tdl  # noqa: E402
 from mc_cnn_amd import hs, train, train_depth, train_mb  # noqa: E402
 from mc_cnn_amd import main as mcmain  # noqa: E402

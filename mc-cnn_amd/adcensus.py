@@ -61,14 +61,31 @@ def census(x0, x1, out, direction):
           "census")
 
 
-def conv3x3(x, weight, bias, relu, out=None):
+CONV_MODES = ("fp32", "bf16x3")
+
+
+def conv3x3(x, weight, bias, relu, out=None, mode="fp32"):
     """cudnn.SpatialConvolution(Cin, Cout, 3, 3, 1, 1, 1, 1) [+ ReLU] of net_te (main.lua:681-686, 727-746) through
-    mc_conv3x3 (fp32 MFMA implicit GEMM).  x (N,Cin,H,W), weight (Cout,Cin,3,3), bias (Cout)."""
+    mc_conv3x3 (fp32 MFMA implicit GEMM).  x (N,Cin,H,W), weight (Cout,Cin,3,3), bias (Cout).
+    mode "bf16x3": an eligible layer (Cin a multiple of 16, Cout <= 128) goes through mc_conv_split of libmcconvsplit.so, which takes every
+    product as three bf16 products of hi + lo parts (include/mc_conv_split.h states the arithmetic; about 1.2e-5 of the output scale
+    from a float64 convolution where mc_conv3x3 is at 8e-7); every other layer goes through mc_conv3x3."""
+    if mode not in CONV_MODES:
+        raise ValueError("conv3x3: mode %r is not one of fp32 | bf16x3" % (mode,))
     _chk(x, weight, bias)
     N, Cin, H, W = x.shape
     Cout = weight.shape[0]
     if out is None:
         out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device)
+    if mode == "bf16x3":
+        from . import _conv_split_lib as csl
+        if csl.eligible(Cin, Cout):
+            split = csl.load()
+            need = split.mc_conv_split_workspace_bytes(Cin, Cout)
+            ws = _scratch_for(x.device, need)
+            csl.check(split.mc_conv_split(_p(x), _p(weight), _p(bias), _p(out), N, Cin, Cout, H, W, 1 if relu else 0, ws.data_ptr(), need,
+                                          _stream()), "conv_split")
+            return out
     need = lib.mc_conv3x3_workspace_bytes(Cin, Cout)
     ws = _scratch_for(x.device, need)
     check(lib.mc_conv3x3(_p(x), _p(weight), _p(bias), _p(out), N, Cin, Cout, H, W, 1 if relu else 0, ws.data_ptr(), need,

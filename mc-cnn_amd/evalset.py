@@ -59,6 +59,9 @@ class EvalSet:
         self.layers = device_layers(layers, device) if self.learned else []
         self.fc_layers = fc_layers if arch == "slow" else None
         self.fc_mode = getattr(opt, "fc_mode", "fp32")        # arch slow's cost stage: main.raw_volumes_slow's fc_mode
+        self.conv_mode = getattr(opt, "conv_mode", "fp32")    # either net's cost stage: main.features_fast / features_slow's conv_mode
+        if self.conv_mode != "fp32" and arch not in ("fast", "slow"):
+            raise ValueError("EvalSet: conv_mode %s for arch %s: it has no net" % (self.conv_mode, arch))
         if self.fc_mode != "fp32" and arch != "slow":
             raise ValueError("EvalSet: fc_mode %s for arch %s: only arch slow has an FC stack" % (self.fc_mode, arch))
         self.border_n = len(self.layers)                      # main.lua:382-391, 923, as main.main sets it
@@ -137,9 +140,9 @@ class EvalSet:
         from . import adcensus, main
         xb, D = e["xb"], e["D"]
         if self.arch == "fast":
-            return dict(feat=main.features_fast(xb, self.layers))
+            return dict(feat=main.features_fast(xb, self.layers, self.conv_mode))
         if self.arch == "slow":
-            return dict(raw=main.raw_volumes_slow(main.features_slow(xb, self.layers), self.fc_layers, D, self.border_n, fc_mode=self.fc_mode))
+            return dict(raw=main.raw_volumes_slow(main.features_slow(xb, self.layers, self.conv_mode), self.fc_layers, D, self.border_n, fc_mode=self.fc_mode))
         cost = adcensus.ad if self.arch == "ad" else adcensus.census   # main.lua:932-942
         volL = torch.empty((1, D, e["H"], e["W"]), dtype=torch.float32, device=self.dev)
         volR = torch.empty_like(volL)

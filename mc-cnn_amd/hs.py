@@ -211,7 +211,10 @@ def parse(argv):
     ap.add_argument("-l1", type=int, default=None, help="arch fast: the convolutions of NET_FNAME, 1..5, where not the data set's")
     from .train_common import add_fc_mode_flag
     add_fc_mode_flag(ap)             # main.py's flag: arch slow's cost stage through mc_fc_stack (fp32) or mc_fc_split_stack (bf16x3)
+    from .train_common import add_conv_mode_flag, check_conv_mode
+    add_conv_mode_flag(ap)           # main.py's flag: the feature net's convolutions of the cost stage (mc_conv3x3 | mc_conv_split)
     opt = ap.parse_args(argv)
+    check_conv_mode(opt, opt.arch, "hs")
     if opt.fc_mode != "fp32" and opt.arch != "slow":
         raise SystemExit("hs: -fc_mode %s for arch %s: only arch slow has an FC stack (main.py -fc_mode)" % (opt.fc_mode, opt.arch))
     if opt.l1 is not None and (opt.arch != "fast" or not 1 <= opt.l1 <= 5):

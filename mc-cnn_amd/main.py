@@ -10,7 +10,9 @@ pipeline in one `mc_predict` call, and writes `left.bin`, `right.bin` (1,D,H,W) 
 with the reference's messages.  `-a time` is main.lua:1140-1167 (min of N runs on an uninitialised batch).
 
 Architectures: fast, slow (feature net + `mc_fc_stack`, main.lua:958-983; `-fc_mode bf16x3` takes the FC stack's products as three
-bf16 products each, `mc_fc_split_stack` of libmcfcsplit.so, wherever arch slow predicts; the default `-fc_mode fp32` is `mc_fc_stack`), ad and census (no net: `mc_ad` / `mc_census_ws`
+bf16 products each, `mc_fc_split_stack` of libmcfcsplit.so, wherever arch slow predicts; the default `-fc_mode fp32` is `mc_fc_stack`;
+`-conv_mode bf16x3` does the same for the 16n -> Cout convolutions of either feature net, `mc_conv_split` of libmcconvsplit.so, default
+`-conv_mode fp32` = `mc_conv3x3`), ad and census (no net: `mc_ad` / `mc_census_ws`
 volumes from the image pair, main.lua:932-942).
 
 -net_fname: the reference's Torch7 `net_*.t7` (main.lua:892-902; read by `t7.py`), an `.npz` with arrays
@@ -44,7 +46,8 @@ import numpy as np
 
 from .binio import write_bin
 from .params import NET_SHAPES, TABLES
-from .train_common import add_fc_mode_flag, add_net_flags, check_fc_mode, check_net_flags, new_parser, pipeline_prm, refuse_net_flags
+from .train_common import (add_conv_mode_flag, add_fc_mode_flag, add_net_flags, check_conv_mode, check_fc_mode, check_net_flags, new_parser,
+                           pipeline_prm, refuse_net_flags)
 
 
 def rgb2y(img):
@@ -86,6 +89,7 @@ def parse(argv):
     ap.add_argument("-disp_max", type=int, default=228 if dataset != "mb" else 200)
     ap.add_argument("-tiny", action="store_true")
     add_fc_mode_flag(ap)
+    add_conv_mode_flag(ap)
     ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
     if dataset in ("kitti", "kitti2015"):
         ap.add_argument("-at", type=int, default=0, choices=(0, 1),
@@ -94,6 +98,7 @@ def parse(argv):
     if arch == "fast":
         check_net_flags(opt, "main.py")
     check_fc_mode(opt, arch, "main.py")
+    check_conv_mode(opt, arch, "main.py")
     if opt.a not in ("predict", "time") and (opt.a not in TRAIN_ACTIONS or dataset not in ("kitti", "kitti2015") or arch != "fast"):
         raise SystemExit("main.py: -a %s is not supported for %s %s; training and testing cover -a %s for "
                          "{kitti|kitti2015} fast only (arch slow trains through train_slow.parse, which main() routes "
@@ -181,12 +186,13 @@ def device_layers(layers, device):
             for wb in layers]
 
 
-def features_slow(x_batch, layers):
-    """forward_free(net_te, x_batch) for arch slow (main.lua:681-686): l1 x [3x3 conv, pad 1, ReLU]."""
+def features_slow(x_batch, layers, conv_mode="fp32"):
+    """forward_free(net_te, x_batch) for arch slow (main.lua:681-686): l1 x [3x3 conv, pad 1, ReLU].  conv_mode: adcensus.conv3x3's
+    mode, "fp32" (mc_conv3x3) or "bf16x3" (mc_conv_split for every layer it takes: all but the first)."""
     from . import adcensus
     h = x_batch.contiguous()
     for w, b in device_layers(layers, h.device):
-        h = adcensus.conv3x3(h, w, b, relu=True)
+        h = adcensus.conv3x3(h, w, b, relu=True, mode=conv_mode)
     return h
 
 
@@ -203,14 +209,15 @@ def raw_volumes_slow(feat, fc_layers, disp_max, border_n, fc_mode="fp32"):
     return vl, vr
 
 
-def features_fast(x_batch, layers):
-    """forward_free(net_te, x_batch) for arch fast (main.lua:945): convs (pad 1) + ReLU between, then Normalize2."""
+def features_fast(x_batch, layers, conv_mode="fp32"):
+    """forward_free(net_te, x_batch) for arch fast (main.lua:945): convs (pad 1) + ReLU between, then Normalize2.  conv_mode: as
+    features_slow's."""
     import torch
     from . import adcensus
     h = x_batch.contiguous()
     layers = device_layers(layers, h.device)
     for i, (w, b) in enumerate(layers):
-        h = adcensus.conv3x3(h, w, b, relu=i < len(layers) - 1)
+        h = adcensus.conv3x3(h, w, b, relu=i < len(layers) - 1, mode=conv_mode)
     norm = torch.empty((h.shape[0], 1) + tuple(h.shape[2:]), dtype=torch.float32, device=h.device)
     out = torch.empty_like(h)
     adcensus.Normalize_forward(h, norm, out)   # Normalize2.lua:8-13 -> adcensus.cu:1310-1333
@@ -258,6 +265,7 @@ def main(argv=None):
     layers = device_layers(load_net(opt.net_fname, dataset, arch, l1=l1), dev) if learned else []   # resident: uploaded once
     fc_layers = load_fc(opt.net_fname, dataset) if arch == "slow" else None
     prm["border_n"] = len(layers)  # (1 + l1*(3-1) - 1) / 2, main.lua:382-391,923
+    conv_mode = getattr(opt, "conv_mode", "fp32")   # the feature net's convolutions wherever this command line predicts
 
     def run(x_batch, D, workspace=None, want_volumes=False):
         if not learned:  # main.lua:932-942: hand-crafted costs straight from the image pair, no border fix
@@ -272,9 +280,9 @@ def main(argv=None):
             cost(x_batch[1:2], x_batch[0:1], volR, 1)
             return stereo_predict_fused(x_batch, prm, D, raw=(volL, volR), workspace=workspace, want_volumes=want_volumes)
         if arch == "fast":
-            return stereo_predict_fused(x_batch, prm, D, feat=features_fast(x_batch, layers), workspace=workspace,
+            return stereo_predict_fused(x_batch, prm, D, feat=features_fast(x_batch, layers, conv_mode), workspace=workspace,
                                         want_volumes=want_volumes)
-        raw = raw_volumes_slow(features_slow(x_batch, layers), fc_layers, D, prm["border_n"], fc_mode=getattr(opt, "fc_mode", "fp32"))
+        raw = raw_volumes_slow(features_slow(x_batch, layers, conv_mode), fc_layers, D, prm["border_n"], fc_mode=getattr(opt, "fc_mode", "fp32"))
         return stereo_predict_fused(x_batch, prm, D, raw=raw, workspace=workspace, want_volumes=want_volumes)
     if opt.a in TRAIN_ACTIONS:
         if mod is None:

@@ -79,10 +79,11 @@ class PairPipeline:
     work of one pair and the GPU work of another overlap, and so do the kernels of two pairs (different streams).  The library is
     re-entrant: one workspace and one scratch area per stream."""
 
-    def __init__(self, prm, layers, disp_max, dev, slots=2):
+    def __init__(self, prm, layers, disp_max, dev, slots=2, conv_mode="fp32"):
         import concurrent.futures
         import torch
         self.prm, self.layers, self.disp_max, self.dev = prm, layers, disp_max, dev
+        self.conv_mode = conv_mode          # main.features_fast's: mc_conv3x3 (fp32) or mc_conv_split (bf16x3) for the inner layers
         self.slots = [dict(stream=torch.cuda.Stream(device=dev), shape=None) for _ in range(max(1, slots))]
         self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=len(self.slots))
         self.next = 0
@@ -109,7 +110,7 @@ class PairPipeline:
         sl["pin_in"].copy_(torch.from_numpy(host))
         with torch.cuda.stream(sl["stream"]):
             xb = sl["pin_in"].to(self.dev, non_blocking=True)
-            res = stereo_predict_fused(xb, self.prm, self.disp_max, feat=mcmain.features_fast(xb, self.layers), workspace=sl["ws"])
+            res = stereo_predict_fused(xb, self.prm, self.disp_max, feat=mcmain.features_fast(xb, self.layers, self.conv_mode), workspace=sl["ws"])
             sl["pin_out"].copy_(res["disp"].reshape(xb.shape[2:]), non_blocking=True)
         sl["stream"].synchronize()
         return sl["pin_out"].numpy().copy()
@@ -128,7 +129,8 @@ class PairPipeline:
         return self.result(self.submit(im0, im1))
 
 
-def main(argv=None):
+def parse(argv=None):
+    from .train_common import add_conv_mode_flag, check_conv_mode
     ap = argparse.ArgumentParser(prog="predict_kitti")
     ap.add_argument("action", choices=["test", "submit"])
     ap.add_argument("-path", default="data.kitti/unzip")
@@ -136,7 +138,14 @@ def main(argv=None):
     ap.add_argument("-disp_max", type=int, default=228)
     ap.add_argument("-n", type=int, default=None, help="number of pairs (default: the reference's 194 / 195)")
     ap.add_argument("-pairs_in_flight", type=int, default=2, help="pairs staged / queued ahead per rank (1: one at a time)")
+    add_conv_mode_flag(ap)           # main.py's flag: the fast net's convolutions
     opt = ap.parse_args(argv)
+    check_conv_mode(opt, "fast", "predict_kitti")
+    return opt
+
+
+def main(argv=None):
+    opt = parse(argv)
     import torch
     import torch.distributed as dist
     from . import main as mcmain
@@ -151,7 +160,7 @@ def main(argv=None):
     layers = mcmain.device_layers(mcmain.load_net(opt.net_fname, "kitti", "fast"), dev)   # resident: uploaded once
     prm = dict(TABLES[("kitti", "fast")])
     prm["border_n"] = len(layers)
-    predict_pair = PairPipeline(prm, layers, opt.disp_max, dev, slots=opt.pairs_in_flight)
+    predict_pair = PairPipeline(prm, layers, opt.disp_max, dev, slots=opt.pairs_in_flight, conv_mode=getattr(opt, "conv_mode", "fp32"))
     err_sum, done = run(opt.action, opt.path, predict_pair, world, rank, n_pairs=opt.n, in_flight=opt.pairs_in_flight)
     if opt.action == "test":
         t = torch.tensor([err_sum, float(done)], dtype=torch.float64, device=dev)

@@ -150,7 +150,7 @@ def save_net(fname, layers, opt):
     mods.append(t7.T7Object("nn.Normalize2", {"train": False}))
     mods.append(t7.T7Object("nn.StereoJoin", {"disp_max": 1, "train": False}))
     net_te = t7.T7Object("nn.Sequential", {"modules": mods, "train": False})
-    opt_t = {k: v for k, v in sorted(vars(opt).items()) if isinstance(v, (bool, int, float, str)) and k != "fc_mode"}   # -fc_mode is how a run predicts, not the net's
+    opt_t = {k: v for k, v in sorted(vars(opt).items()) if isinstance(v, (bool, int, float, str)) and k not in ("fc_mode", "conv_mode")}   # -fc_mode / -conv_mode are how a run predicts, not the net's
     d = os.path.dirname(fname)
     if d:
         os.makedirs(d, exist_ok=True)

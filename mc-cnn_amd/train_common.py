@@ -115,6 +115,31 @@ def check_fc_mode(opt, arch, who):
                                         else "its cost is computed from the image pair"))
 
 
+CONV_MODES = ("fp32", "bf16x3")    # adcensus.conv3x3: mc_conv3x3 | mc_conv_split for the layers it takes (include/mc_conv_split.h)
+
+
+def add_conv_mode_flag(ap):
+    """-conv_mode: how the feature net's 3x3 convolutions take their products wherever a command line predicts with arch fast or arch
+    slow (-a predict | time | test_te | test_all, the test_te after train_tr included).  Not a flag of main.lua; the default is today's
+    fp32 kernel, and training never reads it."""
+    ap.add_argument("-conv_mode", default="fp32", choices=CONV_MODES,
+                    help="the feature net's convolutions: fp32 (mc_conv3x3, exact products) or bf16x3 (mc_conv_split, three bf16 products "
+                         "each, for the layers with 16n input channels; about 1e-5 of the output scale less exact)")
+
+
+def check_conv_mode(opt, arch, who):
+    """-conv_mode bf16x3 where there is no net: refused, naming where it applies.  opt keeps conv_mode only where it is bf16x3, so a
+    command line without the flag (or with -conv_mode fp32) parses to the namespace it parsed to before the flag existed; readers use
+    getattr(opt, "conv_mode", "fp32")."""
+    mode = opt.__dict__.pop("conv_mode", "fp32")
+    if mode == "fp32":
+        return
+    opt.conv_mode = mode
+    if arch not in ("fast", "slow"):
+        raise SystemExit("%s: -conv_mode %s is not supported for arch %s: it has no net (its cost is computed from the image pair); "
+                         "-conv_mode fp32 | bf16x3 is a flag of arch fast and arch slow" % (who, mode, arch))
+
+
 def pipeline_prm(t, opt):
     """The hyper-parameter table of the post-CNN pipeline: t with the 13 flags and the stage switches of opt."""
     prm = dict(t)

@@ -57,6 +57,7 @@ def parse_mb(argv, arch, train_defaults, who):
     ap.add_argument("-subset", type=float, default=1.0, help="main.lua:28; only 1 is supported")
     ap.add_argument("-debug", action="store_true", help="main.lua:18; not supported")
     common.add_fc_mode_flag(ap)       # arch slow: the test_te it runs, the one after train_tr included (main.main's run)
+    common.add_conv_mode_flag(ap)     # either arch: the feature net's convolutions in that test_te
     common.refuse_net_flags(argv, who)
     if arch == "fast":
         common.add_net_flags(ap, "mb", arch)       # -l1 other than 5 trains through train_depth.py: main.route
@@ -64,6 +65,7 @@ def parse_mb(argv, arch, train_defaults, who):
     if arch == "fast":
         common.check_net_flags(opt, who)
     common.check_fc_mode(opt, arch, who)
+    common.check_conv_mode(opt, arch, who)
     if opt.a == "test_all":
         raise SystemExit("%s: -a test_all is not supported on Middlebury (main.lua:1136 asserts the same)" % who)
     if opt.a == "submit":

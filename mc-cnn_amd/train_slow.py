@@ -70,7 +70,7 @@ def save_net(fname, conv_layers, fc_layers, opt):
         last = i == len(fc_layers) - 1
         mods2.append(t7.T7Object("cudnn.Sigmoid" if last else "cudnn.ReLU", {"inplace": True, "train": False}))
     net_te2 = t7.T7Object("nn.Sequential", {"modules": mods2, "train": False})
-    opt_t = {k: v for k, v in sorted(vars(opt).items()) if isinstance(v, (bool, int, float, str)) and k != "fc_mode"}   # -fc_mode is how a run predicts, not the net's
+    opt_t = {k: v for k, v in sorted(vars(opt).items()) if isinstance(v, (bool, int, float, str)) and k not in ("fc_mode", "conv_mode")}   # -fc_mode / -conv_mode are how a run predicts, not the net's
     d = os.path.dirname(fname)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -95,7 +95,9 @@ def parse(argv):
     ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
     ap.add_argument("-at", type=int, default=0, choices=(0, 1), help="1: KITTI 2012 and 2015 together (main.lua:403-426)")
     common.add_fc_mode_flag(ap)       # the test_te / test_all it runs, the one after train_tr included (main.main's run)
+    common.add_conv_mode_flag(ap)     # likewise, the feature net's convolutions
     opt = ap.parse_args(argv[2:])
+    common.check_conv_mode(opt, "slow", "train_slow")
     if opt.a not in ACTIONS:
         raise SystemExit("train_slow: -a %s is not supported for %s slow; training and testing cover -a %s (-a submit is out "
                          "of scope)" % (opt.a, dataset, " | ".join(ACTIONS)))

@@ -1,5 +1,5 @@
-"""The ctypes loader that the four training libraries share.  `_train_lib.py`, `_train_slow_lib.py`, `_train_mb_lib.py` and
-`_train_mb_slow_lib.py` each declare their library (file name, symbol prefix, ABI version, error class, signatures) and bind
+"""The ctypes loader that the training libraries share.  `_train_lib.py`, `_train_slow_lib.py`, `_train_mb_lib.py`,
+`_train_mb_slow_lib.py`, `_train_depth_lib.py` and `_train_slow_depth_lib.py` each declare their library (file name, symbol prefix, ABI version, error class, signatures) and bind
 `load`, `last_error` and `check` from one `Loader`.  There is NO fallback: if the HIP library is missing or fails to load,
 `load()` raises."""
 import ctypes as C

@@ -1,8 +1,9 @@
-// The FC stack of the accurate architecture's training step, shared by train_slow.hip (Linear 224 -> 384 x 4 -> 1) and
-// train_mb_slow.hip (Linear 224 -> 384 x 3 -> 1): batch GEMMs over the R = 2 * n_pairs rows on v_mfma_f32_16x16x4_f32, one wave
+// The FC stack of the accurate architecture's training step, shared by train_slow.hip (Linear 224 -> 384 x 4 -> 1),
+// train_mb_slow.hip (Linear 224 -> 384 x 3 -> 1) and train_slow_depth.hip (Linear 224 -> 384 x l2 -> 1, l2 = 1..7): batch GEMMs over the R = 2 * n_pairs rows on v_mfma_f32_16x16x4_f32, one wave
 // per 16 x 16 tile; the head (last Linear, Sigmoid, BCECriterion2 and their backward passes); the SGD update.  The kernels
-// take their layer by pointer, so the number of hidden Linears is the host's loop count.  Then, over a net N of train_net.h,
-// the FC parameters' offsets, the step's workspace, the launches of the FC stack and the step's argument check.
+// take their layer by pointer, so the number of hidden Linears is the host's loop count.  Then, over a StepShape (a value:
+// that of a net N of train_net.h, or train_slow_depth.hip's with l2 given at run time), the FC parameters' offsets, the step's
+// workspace, the launches of the FC stack and the step's argument check.
 // The including file defines MC_FC_HEAD_MAX_ROWS, the most rows (2 * its MAX_PAIRS) the head kernel keeps in LDS.
 #pragma once
 #include "train_slow_conv.h"
@@ -171,29 +172,53 @@ __device__ __forceinline__ void sgd_update(int j, const float *__restrict__ slab
 	params[j] = params[j] + v;
 }
 
-// ---- the FC stack of a net N: the flat parameter buffer goes on  | fw1 fb1 .. fw(L2) fb(L2) fw(L2+1) fb(L2+1) ------------------
+// ---- the FC stack of a step: the flat parameter buffer goes on  | fw1 fb1 .. fw(L2) fb(L2) fw(L2+1) fb(L2+1) ------------------
 constexpr int NIN = 2 * FM;              // columns of the FC stack's input
 static_assert(NIN % 16 == 0, "16 x 16 tiles");
+constexpr int MAX_L2 = 7;                // the most hidden Linears a step takes: prediction's mc_fc_stack serves 8 layers
 __host__ __device__ constexpr int fc_in(int l) { return l == 1 ? NIN : NH; }
-template <class N> __host__ __device__ constexpr int off_fw(int l) { return n_conv<N>() + (l == 1 ? 0 : NH * NIN + NH + (l - 2) * (NH * NH + NH)); }
-template <class N> __host__ __device__ constexpr int off_fb(int l) { return off_fw<N>(l) + (l == N::L2 + 1 ? NH : NH * fc_in(l)); }
-template <class N> __host__ __device__ constexpr int n_params() { return off_fb<N>(N::L2 + 1) + 1; }
-template <class N, int L = 1> constexpr bool fc_weights_aligned() { if constexpr (L > N::L2) return true; else return off_fw<N>(L) % 4 == 0 && fc_weights_aligned<N, L + 1>(); }
+
+// What the host side of a step knows of its net: the tower through its patch side, patches per workgroup and floats of
+// convolution parameters, and the number of hidden Linears.  A VALUE: train_slow.hip and train_mb_slow.hip make theirs from a
+// net N of train_net.h at compile time (step_shape<N>()), train_slow_depth.hip takes l2 from its caller.  Every offset, the
+// workspace, the FC launches and the argument check below are stated once, over this value.
+struct StepShape {
+	const char *prefix;    // what every message starts with
+	int ps, np, n_conv;    // N::PS, N::NP, n_conv<N>()
+	int l2;                // hidden Linears, 1 .. MAX_L2
+	int max_pairs;         // pairs per batch
+	constexpr int off_fw(int l) const { return n_conv + (l == 1 ? 0 : NH * NIN + NH + (l - 2) * (NH * NH + NH)); }
+	constexpr int off_fb(int l) const { return off_fw(l) + (l == l2 + 1 ? NH : NH * fc_in(l)); }
+	constexpr int n_params() const { return off_fb(l2 + 1) + 1; }
+	constexpr int n_fc() const { return n_params() - n_conv; }
+	constexpr bool fc_weights_aligned() const   // the float4 loads of fc_forward_kernel and fc_backward_kernel
+	{
+		for (int l = 1; l <= l2; ++l)
+			if (off_fw(l) % 4 != 0) return false;
+		return true;
+	}
+};
+template <class N> constexpr StepShape step_shape() { return {N::PREFIX, N::PS, N::NP, n_conv<N>(), N::L2, N::MAX_PAIRS}; }
+template <class N> __host__ __device__ constexpr int off_fw(int l) { return step_shape<N>().off_fw(l); }
+template <class N> __host__ __device__ constexpr int off_fb(int l) { return step_shape<N>().off_fb(l); }
+template <class N> __host__ __device__ constexpr int n_params() { return step_shape<N>().n_params(); }
+template <class N> constexpr bool fc_weights_aligned() { return step_shape<N>().fc_weights_aligned(); }
 
 // the workspace of a step over n pairs; R = 2 n rows of the FC stack
-template <class N> struct Workspace {
+struct StepWorkspace {
 	float *xs;             // (n, 3, PS, PS) sampled patches
-	float *a[N::L2 + 1];   // a[0] (R, 224) the FC input; a[1..L2] (R, 384) the hidden Linears' outputs
+	float *a[MAX_L2 + 1];  // a[0] (R, 224) the FC input; a[1..L2] (R, 384) the hidden Linears' outputs
 	float *g[2];           // (R, 384) output gradients of two consecutive Linears
 	float *dfeat;          // (R, 224) gradient of a[0]
 	float *gfc;            // (NFC) gradient of the FC parameters
 	float *slab;           // (3 n / NP, NCONV) the tower workgroups' gradients of the convolutions
 	size_t floats;
 };
+template <class N> struct Workspace : StepWorkspace {};   // that of a compiled net
 
-template <class N> static Workspace<N> carve(float *base, int n_pairs)
+static StepWorkspace carve(const StepShape &s, float *base, int n_pairs)
 {
-	Workspace<N> ws;
+	StepWorkspace ws = {};
 	size_t o = 0;
 	const size_t R = 2 * (size_t)n_pairs;
 	auto take = [&](size_t n) {
@@ -201,50 +226,77 @@ template <class N> static Workspace<N> carve(float *base, int n_pairs)
 		o += align_up(n, 64);
 		return p;
 	};
-	ws.xs = take((size_t)n_pairs * 3 * N::PS * N::PS);
+	ws.xs = take((size_t)n_pairs * 3 * s.ps * s.ps);
 	ws.a[0] = take(R * NIN);
-	for (int l = 1; l <= N::L2; ++l) ws.a[l] = take(R * NH);
+	for (int l = 1; l <= s.l2; ++l) ws.a[l] = take(R * NH);
 	ws.g[0] = take(R * NH);
 	ws.g[1] = take(R * NH);
 	ws.dfeat = take(R * NIN);
-	ws.gfc = take(n_params<N>() - n_conv<N>());
-	ws.slab = take((size_t)(3 / N::NP) * n_pairs * n_conv<N>());
+	ws.gfc = take(s.n_fc());
+	ws.slab = take((size_t)(3 / s.np) * n_pairs * s.n_conv);
 	ws.floats = o;
 	return ws;
 }
 
-template <class N> static size_t step_workspace_bytes(int n_pairs)
+template <class N> static Workspace<N> carve(float *base, int n_pairs)
 {
-	if (n_pairs < 1 || n_pairs > N::MAX_PAIRS) return 0;
-	return carve<N>(nullptr, n_pairs).floats * sizeof(float);
+	static_assert(N::L2 >= 1 && N::L2 <= MAX_L2, "StepWorkspace's activations");
+	Workspace<N> ws;
+	static_cast<StepWorkspace &>(ws) = carve(step_shape<N>(), base, n_pairs);
+	return ws;
 }
 
-// The launches between the two tower kernels: ws.a[0] -> the hidden Linears, the head (the step's loss), the backward passes
-// -> ws.gfc and ws.dfeat.
-template <class N>
-static int enqueue_fc(const Workspace<N> &ws, const float *params, int n_pairs, float *loss_out, hipStream_t st)
+static size_t step_workspace_bytes(const StepShape &s, int n_pairs)
 {
-	constexpr int L2 = N::L2, NCONV = n_conv<N>();
+	if (n_pairs < 1 || n_pairs > s.max_pairs) return 0;
+	return carve(s, nullptr, n_pairs).floats * sizeof(float);
+}
+
+template <class N> static size_t step_workspace_bytes(int n_pairs) { return step_workspace_bytes(step_shape<N>(), n_pairs); }
+
+// The launches between the two tower kernels: ws.a[0] -> the hidden Linears, the head (the step's loss), the backward passes
+// -> ws.gfc and ws.dfeat.  The head writes ws.g[0]; Linear l reads g[(L2 - l) & 1] and writes the other, so at L2 = 1 the one
+// hidden Linear, which is also the first, reads what the head wrote.
+static int enqueue_fc(const StepShape &s, const StepWorkspace &ws, const float *params, int n_pairs, float *loss_out, hipStream_t st)
+{
+	const int L2 = s.l2, NCONV = s.n_conv;
 	const int R = 2 * n_pairs, mtr = (R + 15) / 16;
 	for (int l = 1; l <= L2; ++l) {
-		fc_forward_kernel<<<cdiv(mtr * (NH / 16), FC_WAVES), FC_WAVES * 64, 0, st>>>(ws.a[l - 1], fc_in(l), params + off_fw<N>(l), params + off_fb<N>(l),
+		fc_forward_kernel<<<cdiv(mtr * (NH / 16), FC_WAVES), FC_WAVES * 64, 0, st>>>(ws.a[l - 1], fc_in(l), params + s.off_fw(l), params + s.off_fb(l),
 		                                                                            ws.a[l], R);
-		if (int rc = check_launch(N::PREFIX, "fc_forward")) return rc;
+		if (int rc = check_launch(s.prefix, "fc_forward")) return rc;
 	}
-	fc_head_kernel<<<1, HEAD_NT, 0, st>>>(ws.a[L2], params + off_fw<N>(L2 + 1), params + off_fb<N>(L2 + 1), R, ws.g[0],
-	                                      ws.gfc + (off_fw<N>(L2 + 1) - NCONV), ws.gfc + (off_fb<N>(L2 + 1) - NCONV), loss_out);
-	if (int rc = check_launch(N::PREFIX, "fc_head")) return rc;
+	fc_head_kernel<<<1, HEAD_NT, 0, st>>>(ws.a[L2], params + s.off_fw(L2 + 1), params + s.off_fb(L2 + 1), R, ws.g[0],
+	                                      ws.gfc + (s.off_fw(L2 + 1) - NCONV), ws.gfc + (s.off_fb(L2 + 1) - NCONV), loss_out);
+	if (int rc = check_launch(s.prefix, "fc_head")) return rc;
 	for (int l = L2; l >= 1; --l) {
 		const int K = fc_in(l), tasks = (mtr + NH / 16) * (K / 16) + NH / 64;
 		const float *g = ws.g[(L2 - l) & 1];
-		float *dw = ws.gfc + (off_fw<N>(l) - NCONV), *db = ws.gfc + (off_fb<N>(l) - NCONV);
+		float *dw = ws.gfc + (s.off_fw(l) - NCONV), *db = ws.gfc + (s.off_fb(l) - NCONV);
 		if (l > 1)
-			fc_backward_kernel<true><<<cdiv(tasks, FC_WAVES), FC_WAVES * 64, 0, st>>>(g, ws.a[l - 1], K, params + off_fw<N>(l), R, ws.g[(L2 + 1 - l) & 1],
+			fc_backward_kernel<true><<<cdiv(tasks, FC_WAVES), FC_WAVES * 64, 0, st>>>(g, ws.a[l - 1], K, params + s.off_fw(l), R, ws.g[(L2 + 1 - l) & 1],
 			                                                                         dw, db);
 		else   // a[0]'s ReLU mask is applied by the tower, which has the activations
-			fc_backward_kernel<false><<<cdiv(tasks, FC_WAVES), FC_WAVES * 64, 0, st>>>(g, ws.a[0], K, params + off_fw<N>(l), R, ws.dfeat, dw, db);
-		if (int rc = check_launch(N::PREFIX, "fc_backward")) return rc;
+			fc_backward_kernel<false><<<cdiv(tasks, FC_WAVES), FC_WAVES * 64, 0, st>>>(g, ws.a[0], K, params + s.off_fw(l), R, ws.dfeat, dw, db);
+		if (int rc = check_launch(s.prefix, "fc_backward")) return rc;
 	}
+	return 0;
+}
+
+template <class N>
+static int enqueue_fc(const Workspace<N> &ws, const float *params, int n_pairs, float *loss_out, hipStream_t st)
+{
+	return enqueue_fc(step_shape<N>(), ws, params, n_pairs, loss_out, st);
+}
+
+static int check_step_args(const StepShape &s, int n_pairs, const float *params, const float *moms, void *ws, size_t ws_bytes)
+{
+	MC_REQUIRE(n_pairs >= 1 && n_pairs <= s.max_pairs, "%s: n_pairs %d outside [1, %d]", s.prefix, n_pairs, s.max_pairs);
+	MC_REQUIRE(params && moms, "%s: null params / momenta", s.prefix);
+	MC_REQUIRE(((uintptr_t)params & 15) == 0, "%s: params not 16-byte aligned", s.prefix);
+	MC_REQUIRE(ws && ws_bytes >= step_workspace_bytes(s, n_pairs), "%s: workspace of %zu bytes, %zu needed", s.prefix, ws_bytes,
+	           step_workspace_bytes(s, n_pairs));
+	MC_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: workspace not 16-byte aligned", s.prefix);
 	return 0;
 }
 
@@ -252,13 +304,7 @@ template <class N>
 static int check_step_args(int n_pairs, const float *params, const float *moms, void *ws, size_t ws_bytes)
 {
 	static_assert(MC_FC_HEAD_MAX_ROWS == 2 * N::MAX_PAIRS, "the head kernel's rows");
-	MC_REQUIRE(n_pairs >= 1 && n_pairs <= N::MAX_PAIRS, "%s: n_pairs %d outside [1, %d]", N::PREFIX, n_pairs, N::MAX_PAIRS);
-	MC_REQUIRE(params && moms, "%s: null params / momenta", N::PREFIX);
-	MC_REQUIRE(((uintptr_t)params & 15) == 0, "%s: params not 16-byte aligned", N::PREFIX);
-	MC_REQUIRE(ws && ws_bytes >= step_workspace_bytes<N>(n_pairs), "%s: workspace of %zu bytes, %zu needed", N::PREFIX, ws_bytes,
-	           step_workspace_bytes<N>(n_pairs));
-	MC_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: workspace not 16-byte aligned", N::PREFIX);
-	return 0;
+	return check_step_args(step_shape<N>(), n_pairs, params, moms, ws, ws_bytes);
 }
 
 }  // namespace mc

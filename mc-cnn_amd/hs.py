@@ -2,6 +2,7 @@
 
     python -m mc_cnn_amd.hs {random|hillclimb_slow|hillclimb_fast|hillclimb_dim} {kitti|kitti2015|mb} {fast|slow|ad|census} test_te
            NET_FNAME [-n N] [-seed S] [-log FILE] [-data_dir D] [-disp_max D] [-cache_gb G] [-in_flight K] [-gpu g] [-no_reuse] [-l1 N]
+           [-l2 N]
 
 hs.py starts a fresh `main.lua` per candidate; here a candidate is `EvalSet.score` (evalset.py): the cost stage of every test
 pair stays on the device, and a candidate costs the post-CNN pipeline plus an error count per pair and one read-back.
@@ -18,6 +19,7 @@ One line per candidate, `score dataset arch action -name value ... -net_fname NE
 -log; hs.py's log files and these are interchangeable.  -n 0 (the default) runs until interrupted, as hs.py does.
 
 -l1 N names the depth of a fast NET_FNAME that `main.py ... -l1 N` trained (1..5); without it the net has the data set's.
+-l2 N names the hidden Linears of a slow NET_FNAME that `main.py ... -l2 N` trained (1..7), likewise.
 
 Not covered: the `train_tr` and `da` searches (of the train_tr grid's axes the depth is trainable here, the feature maps are not:
 fm 64 only), rgs*.py, and an on-disk volume cache (-make_cache / -use_cache).
@@ -164,9 +166,9 @@ def search(method, evalset, grid, n, rng, results, emit=None, **score_args):
 
 
 # ---- the command line -------------------------------------------------------------------------------------------------------------
-def check_net(net_fname, dataset, arch, l1=None):
+def check_net(net_fname, dataset, arch, l1=None, l2=None):
     """([(w, b)], fc layers or None) of NET_FNAME for a learned arch; SystemExit where the file does not fit the arch.  l1: the
-    -l1 of a fast net trained at another depth than the data set's."""
+    -l1 of a fast net trained at another depth than the data set's; l2: the -l2 of a slow net, likewise."""
     from .main import FC_SHAPES, load_fc, load_net
     from .params import NET_SHAPES
     if arch not in ("fast", "slow"):
@@ -175,7 +177,7 @@ def check_net(net_fname, dataset, arch, l1=None):
     l1 = default_l1 if l1 is None else l1
     try:
         layers = load_net(net_fname, dataset, arch, l1=l1)
-        fc = load_fc(net_fname, dataset) if arch == "slow" else None
+        fc = load_fc(net_fname, dataset, l2=l2) if arch == "slow" else None
     except (KeyError, ValueError, OSError) as e:
         raise SystemExit("hs: %s does not fit %s %s: %s" % (net_fname, dataset, arch, e))
     got = [tuple(w.shape) for w, _ in layers]
@@ -183,7 +185,8 @@ def check_net(net_fname, dataset, arch, l1=None):
     if got != want:
         raise SystemExit("hs: %s does not fit %s %s: convolutions of %s, the arch has %s" % (net_fname, dataset, arch, got, want))
     if fc is not None:
-        l2, nh2 = FC_SHAPES[dataset]
+        default_l2, nh2 = FC_SHAPES[dataset]
+        l2 = default_l2 if l2 is None else l2
         dims = [2 * fm] + [nh2] * l2 + [1]
         want = [(dims[i + 1], dims[i]) for i in range(len(dims) - 1)]
         got = [tuple(w.shape) for w, _ in fc]
@@ -209,6 +212,8 @@ def parse(argv):
     ap.add_argument("-gpu", type=int, default=1, help="1-based, as main.py's")
     ap.add_argument("-no_reuse", action="store_true", help="run the whole pipeline for every candidate (no blur-only reuse)")
     ap.add_argument("-l1", type=int, default=None, help="arch fast: the convolutions of NET_FNAME, 1..5, where not the data set's")
+    ap.add_argument("-l2", type=int, default=None, help="arch slow: the hidden Linears of NET_FNAME, 1..7, where not the data set's")
+    ap.add_argument("-nh2", type=int, default=384, help="arch slow: units per hidden Linear; only 384 is supported")
     from .train_common import add_fc_mode_flag
     add_fc_mode_flag(ap)             # main.py's flag: arch slow's cost stage through mc_fc_stack (fp32) or mc_fc_split_stack (bf16x3)
     from .train_common import add_conv_mode_flag, check_conv_mode
@@ -220,6 +225,11 @@ def parse(argv):
     if opt.l1 is not None and (opt.arch != "fast" or not 1 <= opt.l1 <= 5):
         raise SystemExit("hs: -l1 %d for arch %s: -l1 1..5 names the depth of a fast net (main.py -l1); the other archs keep "
                          "their data set's" % (opt.l1, opt.arch))
+    if opt.l2 is not None and (opt.arch != "slow" or not 1 <= opt.l2 <= 7):
+        raise SystemExit("hs: -l2 %d for arch %s: -l2 1..7 names the hidden Linears of a slow net (main.py -l2); the other archs have "
+                         "no FC stack" % (opt.l2, opt.arch))
+    if opt.nh2 != 384:
+        raise SystemExit("hs: -nh2 %d is not supported: only -nh2 384 is (mc_fc_stack and mc_fc_split_stack are 384 wide)" % opt.nh2)
     if opt.action != "test_te":
         grid_of(opt.dataset, opt.arch, opt.action)   # refuses
     if opt.n < 0 or opt.in_flight < 1 or opt.cache_gb < 0:
@@ -231,7 +241,7 @@ def parse(argv):
 def main(argv=None):
     opt = parse(list(sys.argv[1:] if argv is None else argv))
     grid = grid_of(opt.dataset, opt.arch, opt.action)
-    layers, fc_layers = check_net(opt.net_fname, opt.dataset, opt.arch, opt.l1)
+    layers, fc_layers = check_net(opt.net_fname, opt.dataset, opt.arch, opt.l1, opt.l2)
     import torch
     from .evalset import EvalSet
     dev = torch.device("cuda", opt.gpu - 1)

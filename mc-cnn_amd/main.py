@@ -26,6 +26,12 @@ default, sends -a train_tr | train_all through train_depth.py (libmctraindepth.s
 store); `route` is where that is decided.  -L1 is another flag, the cross arm length.  The three flags are refused on slow, ad
 and census.
 
+Arch slow takes main.lua's FC flags: -l2 (hidden Linears, 1..7; default FC_SHAPES: 4 on kitti / kitti2015, 3 on mb) and -nh2 (384
+only: mc_fc_stack and mc_fc_split_stack are 384 wide).  -l2 sizes a `random:` or `.npz` net wherever the command line predicts (a
+`.t7` carries its own depth) and, where it is not the default, sends -a train_tr | train_all through train_slow_depth.py
+(libmctrainslowdepth.so: the accurate net's step with l2 given at run time, on either image store); `route` decides that too.  The
+two flags are refused on fast, ad and census; -l1 / -fm / -ks stay refused on slow.
+
 `-a train_tr | train_all` (kitti | kitti2015; main.lua:602-890) train the net on the GPU from `-data_dir` (arch fast:
 train.py, libmctrain.so; arch slow: train_slow.py, libmctrainslow.so, with train_slow.parse's flags) and save
 net/net_<args>.t7; train_tr then runs test_te.  `training_module` is the one routing table of the four trainable nets, whose
@@ -46,8 +52,8 @@ import numpy as np
 
 from .binio import write_bin
 from .params import NET_SHAPES, TABLES
-from .train_common import (add_conv_mode_flag, add_fc_mode_flag, add_net_flags, check_conv_mode, check_fc_mode, check_net_flags, new_parser,
-                           pipeline_prm, refuse_net_flags)
+from .train_common import (add_conv_mode_flag, add_fc_flags, add_fc_mode_flag, add_net_flags, check_conv_mode, check_fc_flags, check_fc_mode,
+                           check_net_flags, new_parser, pipeline_prm, refuse_fc_flags, refuse_net_flags)
 
 
 def rgb2y(img):
@@ -79,10 +85,13 @@ def parse(argv):
                          "test_all} [flags]  (main.lua:10-13)")
     dataset, arch = argv[0], argv[1]
     refuse_net_flags(argv, "main.py")
+    refuse_fc_flags(argv, "main.py")
     t = TABLES[(dataset, arch)]
     ap = new_parser(dataset, arch, t, FAST_TRAIN_DEFAULTS)
     if arch == "fast":
         add_net_flags(ap, dataset, arch)
+    if arch == "slow":
+        add_fc_flags(ap, dataset)
     ap.add_argument("-a", default="predict", choices=["predict", "time"] + list(TRAIN_ACTIONS) + ["submit"])
     ap.add_argument("-left", default="")
     ap.add_argument("-right", default="")
@@ -97,6 +106,8 @@ def parse(argv):
     opt = ap.parse_args(argv[2:])
     if arch == "fast":
         check_net_flags(opt, "main.py")
+    if arch == "slow":
+        check_fc_flags(opt, "main.py")
     check_fc_mode(opt, arch, "main.py")
     check_conv_mode(opt, arch, "main.py")
     if opt.a not in ("predict", "time") and (opt.a not in TRAIN_ACTIONS or dataset not in ("kitti", "kitti2015") or arch != "fast"):
@@ -156,16 +167,18 @@ def load_net(net_fname, dataset, arch, n_input_plane=1, l1=None):
     return [(z["w%d" % (i + 1)].astype(np.float32), z["b%d" % (i + 1)].astype(np.float32)) for i in range(l1)]
 
 
-def load_fc(net_fname, dataset):
+def load_fc(net_fname, dataset, l2=None):
     """[(w (out,in), b (out))] of net_te2 (arch slow, main.lua:688-695): from the reference's `.t7`, an .npz (fw1,fb1,...)
-    or seeded random."""
+    or seeded random.  l2: the -l2 of a net with another number of hidden Linears than the data set's (a `.t7` carries its own);
+    a random net's layers are drawn in order, so its first ones are the same at every depth."""
     l1, fm = NET_SHAPES[(dataset, "slow")]
     if net_fname.endswith(".t7"):
         fc = reference_nets(net_fname, "slow")[1]
         if not fc:
             raise ValueError("%s: no SpatialConvolution1_fw modules found" % net_fname)
         return fc
-    l2, nh2 = FC_SHAPES[dataset]
+    default_l2, nh2 = FC_SHAPES[dataset]
+    l2 = default_l2 if l2 is None else l2
     dims = [2 * fm] + [nh2] * l2 + [1]
     if net_fname.startswith("random:"):
         rng = np.random.default_rng(int(net_fname.split(":")[1]) + 1)
@@ -239,7 +252,9 @@ def training_module(argv):
 def route(argv):
     """(mod, trainer, dataset, arch, opt, prm) of a command line: mod is `training_module(argv)`, whose `parse` gave the rest
     (None: `parse` above did); trainer is the module whose `train` runs -a train_tr | train_all: train_depth for arch fast with
-    a -l1 other than the data set's (libmctraindepth.so), otherwise mod, or train where mod is None."""
+    a -l1 other than the data set's (libmctraindepth.so), train_slow_depth for arch slow with a -l2 other than the data set's
+    (libmctrainslowdepth.so), otherwise mod, or train where mod is None.  The default depth, written or not, keeps the older
+    libraries."""
     mod = training_module(argv)
     dataset, arch, opt, prm = parse(argv) if mod is None else mod.parse(argv)
     trainer = mod
@@ -248,6 +263,8 @@ def route(argv):
             from . import train_depth as trainer
         elif mod is None:
             from . import train as trainer
+    if arch == "slow" and opt.a in ("train_tr", "train_all") and opt.l2 != FC_SHAPES[dataset][0]:
+        from . import train_slow_depth as trainer
     return mod, trainer, dataset, arch, opt, prm
 
 
@@ -263,7 +280,7 @@ def main(argv=None):
     learned = arch in ("fast", "slow")
     l1 = getattr(opt, "l1", None)         # arch fast: the depth of a random: or .npz net
     layers = device_layers(load_net(opt.net_fname, dataset, arch, l1=l1), dev) if learned else []   # resident: uploaded once
-    fc_layers = load_fc(opt.net_fname, dataset) if arch == "slow" else None
+    fc_layers = load_fc(opt.net_fname, dataset, l2=getattr(opt, "l2", None)) if arch == "slow" else None   # -l2: as -l1 above
     prm["border_n"] = len(layers)  # (1 + l1*(3-1) - 1) / 2, main.lua:382-391,923
     conv_mode = getattr(opt, "conv_mode", "fp32")   # the feature net's convolutions wherever this command line predicts
 

@@ -92,6 +92,39 @@ def check_net_flags(opt, who):
                          % ((who, opt.ks) + L1_TRAINABLE))
 
 
+FC_FLAGS = ("-l2", "-nh2")          # main.lua:76-77, 123-124: what the reference builds the accurate net's FC stack from
+L2_TRAINABLE = (1, 7)               # include/mc_train_slow_depth.h; with the last Linear, the 2..8 layers mc_fc_stack takes
+NH2 = 384                           # the one hidden width of mc_fc_stack, mc_fc_split_stack and the training GEMMs
+
+
+def add_fc_flags(ap, dataset):
+    """-l2 (hidden Linears of arch slow's FC stack, default the data set's) and -nh2 (their units)."""
+    from .main import FC_SHAPES
+    l2, nh2 = FC_SHAPES[dataset]
+    ap.add_argument("-l2", type=int, default=l2, help="hidden Linears of the accurate net, %d..%d" % L2_TRAINABLE)
+    ap.add_argument("-nh2", type=int, default=nh2, help="units per hidden Linear; only %d is supported" % NH2)
+
+
+def refuse_fc_flags(argv, who):
+    """-l2 / -nh2 on a command line whose arch is not slow: the fast net, ad and census have no FC stack."""
+    given = [a for a in argv[2:] if a in FC_FLAGS]
+    if given and len(argv) >= 2 and argv[1] != "slow":
+        why = "the fast net's cost is StereoJoin's dot product" if argv[1] == "fast" else "its cost is computed from the image pair"
+        raise SystemExit("%s: %s is not supported for arch %s: it has no FC stack (%s); -l2 %d..%d (with -nh2 %d) builds "
+                         "{kitti|kitti2015|mb} slow" % ((who, given[0], argv[1], why) + L2_TRAINABLE + (NH2,)))
+
+
+def check_fc_flags(opt, who):
+    """What of -l2 / -nh2 the accurate net's kernels serve; names it where they do not."""
+    if not L2_TRAINABLE[0] <= opt.l2 <= L2_TRAINABLE[1]:
+        raise SystemExit("%s: -l2 %d is not supported: l2 %d..%d are (the training step's head reads a hidden Linear's %d activations, "
+                         "and mc_fc_stack / mc_fc_split_stack take 2..8 layers, the last Linear among them)"
+                         % ((who, opt.l2) + L2_TRAINABLE + (NH2,)))
+    if opt.nh2 != NH2:
+        raise SystemExit("%s: -nh2 %d is not supported: only -nh2 %d is (mc_fc_stack and mc_fc_split_stack are %d wide, and so are "
+                         "the training step's GEMMs); -l2 %d..%d is" % ((who, opt.nh2, NH2, NH2) + L2_TRAINABLE))
+
+
 FC_MODES = ("fp32", "bf16x3")      # fc.fc_cost_volumes: mc_fc_stack | mc_fc_split_stack (include/mc_fc_split.h)
 
 

@@ -59,11 +59,16 @@ def parse_mb(argv, arch, train_defaults, who):
     common.add_fc_mode_flag(ap)       # arch slow: the test_te it runs, the one after train_tr included (main.main's run)
     common.add_conv_mode_flag(ap)     # either arch: the feature net's convolutions in that test_te
     common.refuse_net_flags(argv, who)
+    common.refuse_fc_flags(argv, who)
     if arch == "fast":
         common.add_net_flags(ap, "mb", arch)       # -l1 other than 5 trains through train_depth.py: main.route
+    if arch == "slow":
+        common.add_fc_flags(ap, "mb")              # -l2 other than 3 trains through train_slow_depth.py: main.route
     opt = ap.parse_args(argv[2:])
     if arch == "fast":
         common.check_net_flags(opt, who)
+    if arch == "slow":
+        common.check_fc_flags(opt, who)
     common.check_fc_mode(opt, arch, who)
     common.check_conv_mode(opt, arch, who)
     if opt.a == "test_all":

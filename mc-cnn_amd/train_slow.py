@@ -11,7 +11,8 @@ The initial weights (`init_net`) have the ranges of nn.SpatialConvolution:reset 
 small synthetic sets the net sits on a plateau from there (its output is a constant, the loss stays at ln 2 for thousands
 of steps: README.md); `train(..., init=(conv_layers, fc_layers))` starts from given nets instead.
 
-Middlebury's accurate net (l1 5, l2 3) trains through train_mb_slow.py, `mb fast` through train_mb.py.  Not covered:
+Middlebury's accurate net (l1 5, l2 3) trains through train_mb_slow.py, `mb fast` through train_mb.py, and a -l2 other than 4
+through train_slow_depth.py (libmctrainslowdepth.so; main.route decides).  Not covered:
 -subset, -debug, -a submit.
 """
 import os
@@ -94,10 +95,12 @@ def parse(argv):
     ap.add_argument("-disp_max", type=int, default=228)
     ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
     ap.add_argument("-at", type=int, default=0, choices=(0, 1), help="1: KITTI 2012 and 2015 together (main.lua:403-426)")
+    common.add_fc_flags(ap, dataset)  # -l2 other than 4 trains through train_slow_depth.py: main.route
     common.add_fc_mode_flag(ap)       # the test_te / test_all it runs, the one after train_tr included (main.main's run)
     common.add_conv_mode_flag(ap)     # likewise, the feature net's convolutions
     opt = ap.parse_args(argv[2:])
     common.check_conv_mode(opt, "slow", "train_slow")
+    common.check_fc_flags(opt, "train_slow")
     if opt.a not in ACTIONS:
         raise SystemExit("train_slow: -a %s is not supported for %s slow; training and testing cover -a %s (-a submit is out "
                          "of scope)" % (opt.a, dataset, " | ".join(ACTIONS)))

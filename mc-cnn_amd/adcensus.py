@@ -7,11 +7,15 @@ the SAME tensors (e.g. cross: H,W from `out`, adcensus.cu:336-337) to the C ABI
 (include/mc_adcensus.h) on torch's current stream.  Like the reference, tensors
 must be contiguous fp32 on the GPU; unlike it, that is checked.  A non-zero return
 code raises McError where the reference raises a Lua error.
+
+The training and dataset entries (Normalize_backward_input, Margin2, remove_nonvisible, remove_occluded, remove_white, make_dataset2,
+subset_dataset) go to libmcops.so (include/mc_ops.h), which is loaded at the first call of one of them; they raise OpsError.
 """
 import os
 
 import torch
 
+from . import _ops_lib as _ops
 from ._lib import check, lib
 
 _scratch = {}
@@ -265,6 +269,72 @@ def Normalize_forward(input, norm, output):
     _chk(input, norm, output)
     N, C, H, W = input.shape
     check(lib.mc_normalize_forward(_p(input), _p(norm), _p(output), N, C, H, W, _stream()), "Normalize_forward")
+
+
+# ---- training and dataset operators: libmcops.so (include/mc_ops.h), loaded at the first call ---------------------------------
+
+def _host(t, dtype, what):
+    if not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise TypeError("%s: contiguous %s CPU tensor expected" % (what, str(dtype).replace("torch.", "")))  # luaT_checkudata failure
+    return t.data_ptr()
+
+
+def Normalize_backward_input(grad_output, input, norm, grad_input):
+    """adcensus.Normalize_backward_input(grad_output, input, norm, grad_input) -- adcensus.cu:1359-1377."""
+    _chk(grad_output, input, norm, grad_input)
+    N, C, H, W = input.shape
+    _ops.check(_ops.load().mc_normalize_backward_input(_p(grad_output), _p(input), _p(norm), _p(grad_input), N, C, H, W, _stream()),
+               "Normalize_backward_input")
+
+
+def Margin2(input, tmp, gradInput, margin, pow):
+    """adcensus.Margin2(input, tmp, gradInput, margin, pow) -- adcensus.cu:1425-1453 (the pair count is tmp's)."""
+    _chk(input, tmp, gradInput)
+    _ops.check(_ops.load().mc_margin2(_p(input), _p(tmp), _p(gradInput), tmp.numel(), float(margin), int(pow), _stream()), "Margin2")
+
+
+def remove_nonvisible(y):
+    """adcensus.remove_nonvisible(y) -- adcensus.cu:1734-1745, in place (rows of y:size(4))."""
+    _chk(y)
+    _ops.check(_ops.load().mc_remove_nonvisible(_p(y), y.numel(), y.shape[-1], _stream()), "remove_nonvisible")
+
+
+def remove_occluded(y):
+    """adcensus.remove_occluded(y) -- adcensus.cu:1761-1772, in place; every pixel is tested against the row as it was."""
+    _chk(y)
+    _ops.check(_ops.load().mc_remove_occluded(_p(y), y.numel(), y.shape[-1], _stream()), "remove_occluded")
+
+
+def remove_white(x, y):
+    """adcensus.remove_white(x, y) -- adcensus.cu:1784-1796, in place on y."""
+    _chk(x, y)
+    if x.numel() < y.numel():
+        raise ValueError("remove_white: the image holds %d elements, the map %d" % (x.numel(), y.numel()))
+    _ops.check(_ops.load().mc_remove_white(_p(x), _p(y), y.numel(), _stream()), "remove_white")
+
+
+def make_dataset2(disp, nnz, img, t):
+    """adcensus.make_dataset2(disp, nnz, img, t) -> t -- adcensus.cu:1900-1929: disp (1,1,H,W) and nnz (rows,4) float32 CPU tensors.
+    A list that does not fit in nnz is refused (the reference writes past it)."""
+    import ctypes as C
+    H, W = disp.shape[-2:]
+    out = C.c_int64()
+    _ops.check(_ops.load().mc_make_dataset2(_host(disp, torch.float32, "make_dataset2"), H, W, _host(nnz, torch.float32, "make_dataset2"),
+                                           nnz.numel() // 4, int(img), int(t), C.addressof(out)), "make_dataset2")
+    return out.value
+
+
+def subset_dataset(index, input, output):
+    """adcensus.subset_dataset(index, input, output) -> count -- adcensus.cu:1863-1898: index an int64 CPU tensor of image numbers
+    0..199, input and output (rows,4) float32 CPU tensors.  An index outside 0..199 is refused (the reference writes outside its table)."""
+    import ctypes as C
+    if output.numel() < input.numel():
+        raise ValueError("subset_dataset: the output holds %d elements, the input %d" % (output.numel(), input.numel()))
+    out = C.c_int64()
+    _ops.check(_ops.load().mc_subset_dataset(_host(index, torch.int64, "subset_dataset"), index.numel(),
+                                            _host(input, torch.float32, "subset_dataset"), input.shape[0] if input.dim() else 0,
+                                            _host(output, torch.float32, "subset_dataset"), C.addressof(out)), "subset_dataset")
+    return out.value
 
 
 # ---- cutorch glue used by stereo_predict (not part of adcensus.* in the reference) ----

@@ -233,6 +233,12 @@ enum { MC_SKIP_NONE = 0, MC_SKIP_CBCA = 1, MC_SKIP_SGM = 2, MC_SKIP_OCCLUSION = 
  * two-passes-per-launch kernel) per computed direction. */
 size_t mc_predict_workspace_bytes(const mc_params *p, int C, int D, int H, int W);
 
+/* mc_predict_workspace_bytes plus the SGM's two checkpoint slots (ceil(H / 8) rows of W x D costs per volume, about 2 x 52 MB at
+ * 370 x 1226 x 228).  mc_predict runs on either size and gives the same bits; given this one and D <= 256, its vertical SGM sweeps keep
+ * the down pass at every eighth row in the slots and recompute it where the up pass consumes it, instead of storing and loading it
+ * whole: fewer bytes moved, the faster form. */
+size_t mc_predict_workspace_bytes_full(const mc_params *p, int C, int D, int H, int W);
+
 /* stereo_predict(x_batch, id), main.lua:929-1082, from the cost-volume stage on.
  *   x0,x1    (H,W) normalised left/right images (x_batch[1], x_batch[2]);
  *   featL/R  (C,H,W) normalised features (arch fast: StereoJoin + fix_border,
@@ -242,7 +248,8 @@ size_t mc_predict_workspace_bytes(const mc_params *p, int C, int D, int H, int W
  *   volL_out/volR_out  optional (D,H,W): what left.bin/right.bin hold (main.lua:1042-1047);
  *   dispL0_out/dispR0_out optional (H,W): argmin maps before post-processing;
  *   disp_out (H,W): the returned disparity (main.lua:1081).
- * Runs asynchronously on `stream` inside `workspace`. */
+ * Runs asynchronously on `stream` inside `workspace`: at least mc_predict_workspace_bytes; give it mc_predict_workspace_bytes_full
+ * (the Lua and the Python binding do) -- with the smaller size the result is the same, the vertical SGM sweeps are the slower two launches. */
 int mc_predict(const mc_params *p, const float *x0, const float *x1,
                const float *featL, const float *featR, int C,
                const float *rawL, const float *rawR, int D, int H, int W,

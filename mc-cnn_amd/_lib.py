@@ -15,7 +15,7 @@ SYMBOLS = [
     "mc_cross", "mc_cbca", "mc_cbca_scratch_bytes", "mc_cbca_ws", "mc_sgm2_tmp_bytes", "mc_sgm2", "mc_dhw_to_hwd", "mc_hwd_to_dhw", "mc_scale",
     "mc_argmin", "mc_spatial_argmin", "mc_outlier_detection", "mc_interpolate_occlusion",
     "mc_interpolate_mismatch", "mc_subpixel_enchancement", "mc_median2d", "mc_mean2d", "mc_gaussian_host",
-    "mc_normalize_forward", "mc_predict_workspace_bytes", "mc_predict", "mc_predict_timed",
+    "mc_normalize_forward", "mc_predict_workspace_bytes", "mc_predict_workspace_bytes_full", "mc_predict", "mc_predict_timed",
     "mc_cbca_plan_bytes", "mc_cbca_ws_cfg", "mc_transpose_cfg",
     "mc_read_png16", "mc_write_png16", "mc_write_pfm", "mc_grey2jet", "mc_sgm2_contract_violations",
 ]
@@ -38,6 +38,8 @@ def _load():
     lib.mc_predict_workspace_bytes.restype = C.c_size_t
     lib.mc_conv3x3_workspace_bytes.restype = C.c_size_t
     lib.mc_predict_workspace_bytes.argtypes = [C.POINTER(McParams), C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.mc_predict_workspace_bytes_full.restype = C.c_size_t
+    lib.mc_predict_workspace_bytes_full.argtypes = [C.POINTER(McParams), C.c_int, C.c_int, C.c_int, C.c_int]
     vp, i, f, i64, sz = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
     sig = {
         "mc_fill_nan": [vp, i64, vp],

@@ -399,6 +399,13 @@ size_t mc_predict_workspace_bytes(const mc_params *p, int C, int D, int H, int W
 	return make_plan(p, D, H, W).total;
 }
 
+size_t mc_predict_workspace_bytes_full(const mc_params *p, int C, int D, int H, int W)
+{
+	(void)C;
+	if (!p || !dims_ok(D, H, W) || !(p->blur_sigma > 0)) return 0;
+	return make_plan(p, D, H, W).total_ck;
+}
+
 int mc_predict(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,
                const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
                float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out, float *disp_out, void *stream)
@@ -426,6 +433,10 @@ int mc_predict_timed(const mc_params *p, const float *x0, const float *x1, const
 // the fast path's schedule: 1 / 2 force one lane / two lanes (2: also where the callers' streams alternate), 0 returns to MC_PREDICT_LANES,
 // -1 only asks; returns the one in force
 int mc_test_predict_lanes(int set) { return predict_lanes(set); }
+
+// the fused schedule's vertical launches where both forms apply: 1 forces the down and the up sweep, 2 the checkpoint launch and the recomputing
+// walk, 0 returns to the default (2), -1 only asks; returns the one in force
+int mc_test_sgm_vertical(int mode) { return sgm_vertical(mode); }
 
 // stereo_join_hwd (StereoJoin + fix_border into mc_predict's (H,W,ds) layout) for the chosen volumes: sides bit 0 left, bit 1 right
 int mc_test_stereo_join_hwd(const float *featL, const float *featR, float *volL, float *volR, int C, int D, int ds, int H, int W, int border_n,

@@ -77,6 +77,16 @@ int sgm_contract_violations(const float *vol, int H, int W, int D, unsigned *cou
 int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
                const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,
                float alpha1, float q1, float q2, bool fused, unsigned drop_final, bool tri, hipStream_t st);
+// sgm_sweeps for a caller that has checkpoint slots: ck[v] (sgm_ck_bytes, 16-byte aligned) belongs to volume v, or ck is null.  With slots, fused,
+// D <= 256 and volumes below 2 GiB, the vertical launches recompute the down pass: L_down is kept at every SGM_CK_ROWS-th row only, in ck[v].
+// sgm_sweeps is this with ck = null.  Declared weak: a program that links predict.hip without sgm.hip behind a stub of sgm_sweeps (the host check
+// of the two lanes) has no definition, and predict_impl then calls sgm_sweeps.
+constexpr int SGM_CK_ROWS = 8;
+static inline size_t sgm_ck_bytes(int H, int W, int ds) { return ((size_t)((H + SGM_CK_ROWS - 1) / SGM_CK_ROWS) * W * ds * sizeof(float) + 255) / 256 * 256; }
+int sgm_sweeps_ck(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
+                  const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,
+                  float alpha1, float q1, float q2, bool fused, unsigned drop_final, bool tri, float *const ck[2], hipStream_t st) __attribute__((weak));
+int sgm_vertical(int set = -1);   // set 1 / 2: force the two-launch / the recomputing form where it applies (the tests), 0: back to the default (2); returns the one in force
 
 // predict.hip
 static inline int gaussian_ks(double sigma) { return 2 * (int)ceil(sigma * 3) + 1; }   // main.lua:529-530
@@ -86,11 +96,13 @@ void gaussian_fill(double sigma, float *k);
 struct Plan {
 	int Dp;                 // padded pixel stride of the (H,W,Dp) volumes
 	size_t cplan_bytes;     // per direction: the tile kernel's plan (cbca_tile.hip), 0 where it would not be reused
-	size_t total;
+	size_t total;           // what mc_predict needs
+	size_t total_ck;        // ... and with the SGM's checkpoint slots behind it, what it takes to run the recomputing vertical launches
 	void *maps, *packed;
 	float *x0c, *x1c, *img[6], *gk;   // gk: unused (the Gaussian table has its own device memory); kept so that the layout stays
 	float *bufA[2], *bufB[2], *bufC[2];   // ping-pong per side; bufC: scratch of the SGM's concurrent second direction and of pairs of CBCA passes
 	void *cplan[2];             // null where the direction has none
+	float *ck[2];               // the SGM's checkpoint rows of the left and of the right volume (sgm_ck_bytes each): behind `total`, there in a workspace of total_ck bytes
 };
 Plan make_plan(const mc_params *p, int D, int H, int W, void *base = nullptr);
 

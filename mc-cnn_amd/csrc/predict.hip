@@ -188,6 +188,9 @@ Plan make_plan(const mc_params *p, int D, int H, int W, void *base)
 	pl.gk = (float *)take(align_up((size_t)ks * ks * sizeof(float), 256));
 	for (int v = 0; v < 2; ++v) pl.cplan[v] = (pl.cplan_bytes && v < nplan) ? take(pl.cplan_bytes) : nullptr;
 	pl.total = off;
+	// the optional tail: mc_predict_workspace_bytes stays what it was (a workspace of that size runs the down and the up sweep)
+	for (float *&ck : pl.ck) ck = (float *)take(sgm_ck_bytes(H, W, pl.Dp));
+	pl.total_ck = off;
 	return pl;
 }
 
@@ -234,6 +237,8 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	const Plan pl = make_plan(p, D, H, W, workspace);   // (addresses only: nothing is touched before the two checks)
 	MC_REQUIRE(workspace_bytes >= pl.total, "mc_predict: workspace %zu < %zu bytes", workspace_bytes, pl.total);
 	MC_REQUIRE((uintptr_t)workspace % 256 == 0, "mc_predict: workspace must be 256-byte aligned");
+
+	const bool have_ck = workspace_bytes >= pl.total_ck && sgm_sweeps_ck != nullptr;   // the workspace holds the SGM's checkpoint slots
 
 	const int64_t HW = (int64_t)H * W;
 	const int64_t V = (int64_t)D * HW;
@@ -327,10 +332,11 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 			// out:zero(); sgm2(...); vol:copy(out):div(4)  (main.lua:1013-1018): the zero is folded
 			// into the first sweep (0 + L_0) and the /4 into the last
 			const float *Cv[2];
-			float *outv[2], *scratch[2], *dv[2];
+			float *outv[2], *scratch[2], *dv[2], *ckv[2] = {nullptr, nullptr};
 			int dir[2];
 			for (int k = 0; k < nv; ++k) {
 				Cv[k] = cur[v0 + k]; outv[k] = other(v0 + k); scratch[k] = pl.bufC[v0 + k]; dv[k] = dispv[v0 + k]; dir[k] = direction[v0 + k];
+				ckv[k] = pl.ck[v0 + k];
 			}
 			const bool am = (it == n_sgm - 1) && n_cbca2 == 0;
 			// the right volume's final costs: where no CBCA-2 follows, only right.bin reads them (sub-pixel refinement reads the
@@ -338,8 +344,10 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 			// sgm_sweeps counts its bits from the first volume it is given: bit 1 of a pair, bit 0 of the right volume alone
 			const bool has_right = v0 + nv == 2;
 			const unsigned drop_final = (am && has_right && !volR_out) ? 1u << (1 - v0) : 0u;
-			const int rc1 = sgm_sweeps(Cv, outv, scratch, am ? dv : nullptr, dir, nv, H, W, D, ds, pl.maps, p->pi1, p->pi2, p->alpha1,
-			                           p->sgm_q1, p->sgm_q2, true, drop_final, nan_triangle, s);
+			const int rc1 = have_ck ? sgm_sweeps_ck(Cv, outv, scratch, am ? dv : nullptr, dir, nv, H, W, D, ds, pl.maps, p->pi1, p->pi2, p->alpha1,
+			                                        p->sgm_q1, p->sgm_q2, true, drop_final, nan_triangle, ckv, s)
+			                        : sgm_sweeps(Cv, outv, scratch, am ? dv : nullptr, dir, nv, H, W, D, ds, pl.maps, p->pi1, p->pi2, p->alpha1,
+			                                     p->sgm_q1, p->sgm_q2, true, drop_final, nan_triangle, s);
 			if (rc1) return rc1;
 			have_disp = am;
 			for (int k = 0; k < nv; ++k) cur[v0 + k] = outv[k];

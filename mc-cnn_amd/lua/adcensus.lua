@@ -74,6 +74,7 @@ typedef struct mc_params {
 	int left_only;
 } mc_params;
 size_t mc_predict_workspace_bytes(const mc_params *p, int C, int D, int H, int W);
+size_t mc_predict_workspace_bytes_full(const mc_params *p, int C, int D, int H, int W);
 int mc_predict(const mc_params *p, const float *x0, const float *x1,
                const float *featL, const float *featR, int C,
                const float *rawL, const float *rawR, int D, int H, int W,
@@ -301,8 +302,9 @@ function adcensus.predict(o, dataset, arch, x_batch, input, disp_max, border_n, 
    p.left_only = (not both and dataset == 'mb') and 1 or 0   -- mb_directions, main.lua:953-955: dataset mb outside `-a predict` only
    local H, W = x_batch:size(3), x_batch:size(4)
    local C = arch == 'fast' and input:size(2) or 0
-   local need = tonumber(lib.mc_predict_workspace_bytes(p, C, disp_max, H, W))
-   if need == 0 then error('mc_predict_workspace_bytes: bad arguments', 2) end
+   if tonumber(lib.mc_predict_workspace_bytes(p, C, disp_max, H, W)) == 0 then error('mc_predict_workspace_bytes: bad arguments', 2) end
+   -- what is allocated is the full size: that plus the SGM's checkpoint slots, at which mc_predict runs its faster vertical sweeps
+   local need = tonumber(lib.mc_predict_workspace_bytes_full(p, C, disp_max, H, W))
    if predict_ws:nElement() * 4 < need + 256 then predict_ws:resize(math.ceil((need + 256) / 4)) end
    local ws = ffi.cast('char *', predict_ws:data())
    ws = ws + (256 - tonumber(ffi.cast('uintptr_t', ws)) % 256) % 256      -- mc_predict wants a 256-byte aligned workspace

@@ -98,20 +98,24 @@ def stereo_predict(x_batch, params, disp_max, feat=None, raw=None, return_all=Fa
     return d
 
 
-def workspace_bytes(params, disp_max, H, W, C_feat=0):
+def workspace_bytes(params, disp_max, H, W, C_feat=0, full=False):
+    """what mc_predict needs; full: with the SGM's checkpoint slots behind it, the size at which it runs its faster vertical sweeps"""
     p = make_params(params)
-    n = lib.mc_predict_workspace_bytes(C.byref(p), int(C_feat), int(disp_max), int(H), int(W))
+    fn = lib.mc_predict_workspace_bytes_full if full else lib.mc_predict_workspace_bytes
+    n = fn(C.byref(p), int(C_feat), int(disp_max), int(H), int(W))
     if n == 0:
         raise ValueError("mc_predict_workspace_bytes: bad arguments")
     return n
 
 
 class Workspace:
-    """Caller-owned device scratch for mc_predict (one per concurrent stream)."""
+    """Caller-owned device scratch for mc_predict (one per concurrent stream): nbytes is what mc_predict needs, nbytes_full what is
+    allocated and handed to it -- the SGM's checkpoint slots lie behind nbytes."""
 
     def __init__(self, params, disp_max, H, W, device):
         self.nbytes = workspace_bytes(params, disp_max, H, W)
-        self.buf = torch.empty(self.nbytes + 256, dtype=torch.uint8, device=device)
+        self.nbytes_full = workspace_bytes(params, disp_max, H, W, full=True)
+        self.buf = torch.empty(self.nbytes_full + 256, dtype=torch.uint8, device=device)
         off = (-self.buf.data_ptr()) % 256
         self.ptr = self.buf.data_ptr() + off
 
@@ -138,11 +142,12 @@ def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspa
         keep = (raw[0].contiguous(), raw[1].contiguous())
         rl, rr = keep[0].data_ptr(), keep[1].data_ptr()
     st = torch.cuda.current_stream().cuda_stream
+    ws_bytes = getattr(workspace, "nbytes_full", workspace.nbytes)
     res = dict(disp=out)
     if timed:
         ms = (C.c_float * 8)()
         check(lib.mc_predict_timed(C.byref(p), x0.data_ptr(), x1.data_ptr(), fl, fr, Cn, rl, rr, D, H, W, workspace.ptr,
-                                   workspace.nbytes, out.data_ptr(), st, ms), "mc_predict_timed")
+                                   ws_bytes, out.data_ptr(), st, ms), "mc_predict_timed")
         res["stage_ms"] = dict(zip(STAGES, list(ms)))
         return res
     vl = vr = dl = dr = None
@@ -155,6 +160,6 @@ def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspa
         res["dispR0"] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
         dl, dr = res["dispL0"].data_ptr(), res["dispR0"].data_ptr()
     check(lib.mc_predict(C.byref(p), x0.data_ptr(), x1.data_ptr(), fl, fr, Cn, rl, rr, D, H, W, workspace.ptr,
-                         workspace.nbytes, vl, vr, dl, dr, out.data_ptr(), st), "mc_predict")
+                         ws_bytes, vl, vr, dl, dr, out.data_ptr(), st), "mc_predict")
     del keep
     return res

@@ -29,6 +29,7 @@ INVENTORY_FC_SPLIT = os.path.join(ROOT, "tests", "kernel_inventory_fc_split.txt"
 INVENTORY_CONV_SPLIT = os.path.join(ROOT, "tests", "kernel_inventory_conv_split.txt")   # libmcconvsplit.so
 INVENTORY_TRAIN_SLOW_DEPTH = os.path.join(ROOT, "tests", "kernel_inventory_train_slow_depth.txt")   # libmctrainslowdepth.so (the FC kernels' names again)
 INVENTORY_OPS = os.path.join(ROOT, "tests", "kernel_inventory_ops.txt")                 # libmcops.so
+INVENTORY_SGM_RECOMPUTE = os.path.join(ROOT, "tests", "kernel_inventory_sgm_recompute.txt")   # libmcsgmrecompute.so
 NAMESPACE = "mc::"
 
 
@@ -91,7 +92,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("stats", nargs="+", help="kernel_stats.csv of rocprofv3 --kernel-trace --stats")
     ap.add_argument("--inventory", nargs="+", default=[INVENTORY, INVENTORY_TRAIN_SLOW, INVENTORY_TRAIN_MB, INVENTORY_TRAIN_MB_SLOW, INVENTORY_EVAL,
-                                                              INVENTORY_TRAIN_DEPTH, INVENTORY_TRAIN_SLOW_DEPTH, INVENTORY_OPS, INVENTORY_CONV_SPLIT, INVENTORY_FC_SPLIT])
+                                                              INVENTORY_TRAIN_DEPTH, INVENTORY_TRAIN_SLOW_DEPTH, INVENTORY_OPS, INVENTORY_CONV_SPLIT, INVENTORY_SGM_RECOMPUTE, INVENTORY_FC_SPLIT])
     a = ap.parse_args(argv)
     inv = {}
     for path in a.inventory:

@@ -8,7 +8,10 @@ from .params import McParams
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmcadcensus.so")
 
-# every symbol include/mc_adcensus.h declares
+# include/mc_adcensus.h
+PREFIX = "mc"
+ABI_VERSION = 8
+# every symbol it declares
 SYMBOLS = [
     "mc_version", "mc_last_error", "mc_fill_nan", "mc_stereo_join", "mc_ad", "mc_census_scratch_bytes", "mc_census_ws", "mc_fc_stack_workspace_bytes", "mc_fc_stack", "mc_conv3x3_workspace_bytes", "mc_conv3x3",
     "mc_fix_border",
@@ -89,7 +92,7 @@ def _load():
         if name not in ("mc_sgm2_tmp_bytes", "mc_cbca_scratch_bytes", "mc_cbca_plan_bytes", "mc_census_scratch_bytes",
                         "mc_fc_stack_workspace_bytes", "mc_conv3x3_workspace_bytes"):
             fn.restype = C.c_int
-    if lib.mc_version() != 8:
+    if lib.mc_version() != ABI_VERSION:
         raise ImportError("mc-cnn_amd: ABI version mismatch")
     return lib
 

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""Which of the kernels of libmcadcensus.so and libmctrain.so a profiled run launched.
+"""Which of the libraries' kernels a profiled run launched.
 
     scripts/kernel_coverage.py KERNEL_STATS_CSV [KERNEL_STATS_CSV ...] [--inventory FILE ...]   (default: the inventory files under tests/)
 
 Reads the kernel_stats.csv files that `rocprofv3 --kernel-trace --stats` writes (e.g. for `pytest tests -m gpu`), normalises the
-kernel names the way tests/kernel_inventory.txt lists them, and prints the inventory kernels the run never launched and the
-library kernels it launched that the inventory does not list.  Only the two libraries' own kernels (namespace mc::) count, those of
-libmctrain.so (training, dataset preparation) like those of libmcadcensus.so: torch's and the reference's kernels of the same run
-are ignored.  Exit status 1 if either list is not empty.
+kernel names the way the inventory files list them, and prints the inventory kernels the run never launched and the library kernels
+it launched that no inventory lists.  The inventory files are tests/kernel_inventory*.txt, one per library (the two oldest libraries
+share tests/kernel_inventory.txt); tests/libraries.py says which library each serves.  Only the libraries' own kernels (namespace mc::)
+count: torch's and the reference's kernels of the same run are ignored.  Exit status 1 if either list is not empty.
 
 A name is normalised by dropping `void`, the namespaces, `__device_stub__` (nm's spelling of a kernel's host stub) and the argument
 list: `void mc::sgm_pass_kernel<0, 4, 0, false, true, 8, true, false>(mc::SgmPassArgs)` -> `sgm_pass_kernel<0, 4, 0, false, true,
@@ -15,22 +15,18 @@ list: `void mc::sgm_pass_kernel<0, 4, 0, false, true, 8, true, false>(mc::SgmPas
 """
 import argparse
 import csv
+import glob
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVENTORY = os.path.join(ROOT, "tests", "kernel_inventory.txt")
-INVENTORY_TRAIN_SLOW = os.path.join(ROOT, "tests", "kernel_inventory_train_slow.txt")   # libmctrainslow.so
-INVENTORY_TRAIN_MB = os.path.join(ROOT, "tests", "kernel_inventory_train_mb.txt")       # libmctrainmb.so
-INVENTORY_TRAIN_MB_SLOW = os.path.join(ROOT, "tests", "kernel_inventory_train_mb_slow.txt")   # libmctrainmbslow.so (shares the FC kernels' names with libmctrainslow.so)
-INVENTORY_EVAL = os.path.join(ROOT, "tests", "kernel_inventory_eval.txt")               # libmceval.so
-INVENTORY_TRAIN_DEPTH = os.path.join(ROOT, "tests", "kernel_inventory_train_depth.txt")   # libmctraindepth.so
-INVENTORY_FC_SPLIT = os.path.join(ROOT, "tests", "kernel_inventory_fc_split.txt")       # libmcfcsplit.so
-INVENTORY_CONV_SPLIT = os.path.join(ROOT, "tests", "kernel_inventory_conv_split.txt")   # libmcconvsplit.so
-INVENTORY_TRAIN_SLOW_DEPTH = os.path.join(ROOT, "tests", "kernel_inventory_train_slow_depth.txt")   # libmctrainslowdepth.so (the FC kernels' names again)
-INVENTORY_OPS = os.path.join(ROOT, "tests", "kernel_inventory_ops.txt")                 # libmcops.so
-INVENTORY_SGM_RECOMPUTE = os.path.join(ROOT, "tests", "kernel_inventory_sgm_recompute.txt")   # libmcsgmrecompute.so
 NAMESPACE = "mc::"
+
+
+def inventories():
+    """every inventory file under tests/"""
+    return sorted(glob.glob(os.path.join(ROOT, "tests", "kernel_inventory*.txt")))
 
 
 def normalise(name):
@@ -91,8 +87,7 @@ def launched(csv_paths):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("stats", nargs="+", help="kernel_stats.csv of rocprofv3 --kernel-trace --stats")
-    ap.add_argument("--inventory", nargs="+", default=[INVENTORY, INVENTORY_TRAIN_SLOW, INVENTORY_TRAIN_MB, INVENTORY_TRAIN_MB_SLOW, INVENTORY_EVAL,
-                                                              INVENTORY_TRAIN_DEPTH, INVENTORY_TRAIN_SLOW_DEPTH, INVENTORY_OPS, INVENTORY_CONV_SPLIT, INVENTORY_SGM_RECOMPUTE, INVENTORY_FC_SPLIT])
+    ap.add_argument("--inventory", nargs="+", default=inventories())
     a = ap.parse_args(argv)
     inv = {}
     for path in a.inventory:

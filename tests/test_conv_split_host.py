@@ -16,26 +16,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import conv_split_oracle as co  # noqa: E402
+import libraries as L  # noqa: E402
 from mc_cnn_amd import _conv_split_lib as csl  # noqa: E402
 from mc_cnn_amd import hs, predict_kitti, train, train_mb, train_mb_slow, train_slow  # noqa: E402
 from mc_cnn_amd import main as mcmain  # noqa: E402
 
 HEADER = os.path.join(ROOT, "include", "mc_conv_split.h")
-MAKEFILE = os.path.join(ROOT, "mc-cnn_amd", "csrc", "Makefile")
 
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------
 def test_library_loads_without_a_gpu_and_exports_exactly_the_headers_symbols():
-    lib = csl.load()
+    """what only libmcconvsplit.so has; tests/test_libraries_host.py holds it to the contract of every library"""
     text = open(HEADER).read()
-    assert lib.mc_conv_split_version() == csl.ABI_VERSION == int(re.search(r"#define MC_CONV_SPLIT_ABI_VERSION (\d+)", text).group(1)) == 1
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(mc_conv_split\w*)\s*\(", code))
-    out = subprocess.check_output(["nm", "-D", "--defined-only", csl.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] in "TtDBW" and
-                line.split()[-1].startswith("mc_")}
-    assert exported == declared == set(csl.SYMBOLS) == {"mc_conv_split_version", "mc_conv_split_last_error", "mc_conv_split_workspace_bytes",
-                                                        "mc_conv_split"}
+    assert csl.load().mc_conv_split_version() == csl.ABI_VERSION == 1
+    assert L.exported_abi(csl.LIB_PATH) == {"mc_conv_split_version", "mc_conv_split_last_error", "mc_conv_split_workspace_bytes", "mc_conv_split"}
     assert re.search(r"#define MC_CONV_SPLIT_CIN_STEP %d\b" % csl.CIN_STEP, text) and re.search(r"#define MC_CONV_SPLIT_MAX_COUT %d\b" % csl.MAX_COUT, text)
     assert (csl.CIN_STEP, csl.MAX_COUT, csl.EINVAL) == (16, 128, -22) and os.path.basename(csl.LIB_PATH) == "libmcconvsplit.so"
     assert "Inputs are finite" in text and "round to nearest even" in text
@@ -95,43 +89,12 @@ def test_every_refusal_returns_einval_with_its_message_before_any_launch():
         csl.check(call(Cin=40), "mc_conv_split")
 
 
-def test_the_makefile_builds_the_library_on_an_all_line_of_its_own():
-    text = open(MAKEFILE).read()
-    alls = [line.split(":", 1)[1].split() for line in text.splitlines() if line.startswith("all:")]
-    assert len(alls[0]) == 6 and "$(CONV_SPLIT_LIB)" not in alls[0]                # what tests/test_hs_host.py reads
-    assert ["$(CONV_SPLIT_LIB)"] in alls[1:] and ["$(FC_SPLIT_LIB)"] in alls[1:] and ["$(TRAIN_DEPTH_LIB)"] in alls[1:]
-    assert re.search(r"^CONV_SPLIT_LIB = \.\./libmcconvsplit\.so$", text, re.M) and re.search(r"^CONV_SPLIT_OBJS = conv_split\.o$", text, re.M)
-    assert re.search(r"^\$\(CONV_SPLIT_LIB\): \$\(CONV_SPLIT_OBJS\) error\.o$", text, re.M)
-    hdrs = re.search(r"^HDRS = ((?:.*\\\n)*.*)$", text, re.M).group(1)
-    assert "../../include/mc_conv_split.h" in hdrs.replace("\\", " ").split()
-    assert os.path.isfile(csl.LIB_PATH) and os.path.isfile(os.path.join(ROOT, "mc-cnn_amd", "csrc", "conv_split.hip"))
-    out = subprocess.check_output(["make", "-n", "-B", "-C", os.path.dirname(MAKEFILE), "../libmcconvsplit.so"]).decode()
+def test_the_library_is_built_from_its_own_unit_and_holds_its_own_kernels():
+    assert L.print_libraries()["libmcconvsplit.so"] == ["conv_split.o", "error.o"]
+    out = L.make("-n", "-B", "../libmcconvsplit.so")
     assert "conv_split.hip" in out and "error.hip" in out and "-o ../libmcconvsplit.so" in out and "conv3x3.hip" not in out
-    out = subprocess.check_output(["make", "-n", "-B", "-C", os.path.dirname(MAKEFILE), "../libmcadcensus.so"]).decode()
-    assert "conv_split" not in out                                                 # libmcadcensus.so keeps its kernel set
-
-
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(kc.INVENTORY_CONV_SPLIT)
-    out = subprocess.check_output(["nm", "-C", csl.LIB_PATH]).decode()
-    built = {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-    assert built == set(inv) == {"conv_split_prep_kernel", "conv_split_kernel<1>", "conv_split_kernel<2>"}
-    others = set()                   # a library of its own: no kernel name of the other inventories, which stay as they are
-    for path in (kc.INVENTORY, kc.INVENTORY_TRAIN_SLOW, kc.INVENTORY_TRAIN_MB, kc.INVENTORY_TRAIN_MB_SLOW, kc.INVENTORY_EVAL,
-                 kc.INVENTORY_TRAIN_DEPTH, kc.INVENTORY_FC_SPLIT):
-        others |= set(kc.read_inventory(path))
-    assert not built & others
-    assert "INVENTORY_CONV_SPLIT," in open(os.path.join(ROOT, "scripts", "kernel_coverage.py")).read()    # among --inventory's defaults
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(ROOT, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)
+    assert "conv_split" not in L.make("-n", "-B", "../libmcadcensus.so")             # libmcadcensus.so keeps its kernel set
+    assert L.built_kernels(csl.LIB_PATH) == {"conv_split_prep_kernel", "conv_split_kernel<1>", "conv_split_kernel<2>"}
 
 
 # ---- the flag ------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,6 @@ the arithmetic's restatement (tests/fc_split_oracle.py) against the exact-produc
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 import types
 
@@ -15,12 +14,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fc_split_oracle as fo  # noqa: E402
+import libraries as L  # noqa: E402
 from mc_cnn_amd import _fc_split_lib as fsl  # noqa: E402
 from mc_cnn_amd import hs, train_mb, train_mb_slow, train_slow  # noqa: E402
 from mc_cnn_amd import main as mcmain  # noqa: E402
 
 HEADER = os.path.join(ROOT, "include", "mc_fc_split.h")
-MAKEFILE = os.path.join(ROOT, "mc-cnn_amd", "csrc", "Makefile")
 FC_CASES = [(8, 5, 50, 10, 3), (16, 3, 100, 7, 2), (112, 2, 40, 48, 3), (4, 9, 97, 5, 1)]     # tests/test_gpu_fc.py::test_fc_stack
 
 
@@ -33,16 +32,10 @@ def fc_inputs(C_, H, W, n_hidden):
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------
 def test_library_loads_without_a_gpu_and_exports_exactly_the_headers_symbols():
-    lib = fsl.load()
+    """what only libmcfcsplit.so has; tests/test_libraries_host.py holds it to the contract of every library"""
     text = open(HEADER).read()
-    assert lib.mc_fc_split_version() == fsl.ABI_VERSION == int(re.search(r"#define MC_FC_SPLIT_ABI_VERSION (\d+)", text).group(1)) == 1
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(mc_fc_split_\w+)\s*\(", code))
-    out = subprocess.check_output(["nm", "-D", "--defined-only", fsl.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] in "TtDBW" and
-                line.split()[-1].startswith("mc_")}
-    assert exported == declared == set(fsl.SYMBOLS) == {"mc_fc_split_version", "mc_fc_split_last_error", "mc_fc_split_workspace_bytes",
-                                                        "mc_fc_split_stack"}
+    assert fsl.load().mc_fc_split_version() == fsl.ABI_VERSION == 1
+    assert L.exported_abi(fsl.LIB_PATH) == {"mc_fc_split_version", "mc_fc_split_last_error", "mc_fc_split_workspace_bytes", "mc_fc_split_stack"}
     assert re.search(r"#define MC_FC_SPLIT_NH %d\b" % fsl.NH, text) and re.search(r"#define MC_FC_SPLIT_VOXELS %d\b" % fsl.VOXELS, text)
     assert (fsl.NH, fsl.EINVAL) == (384, -22) and os.path.basename(fsl.LIB_PATH) == "libmcfcsplit.so"
 
@@ -106,41 +99,12 @@ def test_every_refusal_returns_einval_with_its_message_before_any_launch():
         fsl.check(call(widths=(384, 256, 384, 1)), "mc_fc_split_stack")
 
 
-def test_the_makefile_builds_the_library_on_an_all_line_of_its_own():
-    text = open(MAKEFILE).read()
-    alls = [line.split(":", 1)[1].split() for line in text.splitlines() if line.startswith("all:")]
-    assert len(alls[0]) == 6 and "$(FC_SPLIT_LIB)" not in alls[0]                  # what tests/test_hs_host.py reads
-    assert ["$(FC_SPLIT_LIB)"] in alls[1:]
-    assert re.search(r"^FC_SPLIT_LIB = \.\./libmcfcsplit\.so$", text, re.M) and re.search(r"^FC_SPLIT_OBJS = fc_split\.o$", text, re.M)
-    assert re.search(r"^\$\(FC_SPLIT_LIB\): \$\(FC_SPLIT_OBJS\) error\.o$", text, re.M)
-    hdrs = re.search(r"^HDRS = ((?:.*\\\n)*.*)$", text, re.M).group(1)
-    assert "../../include/mc_fc_split.h" in hdrs.replace("\\", " ").split()
-    assert os.path.isfile(fsl.LIB_PATH) and os.path.isfile(os.path.join(ROOT, "mc-cnn_amd", "csrc", "fc_split.hip"))
-    out = subprocess.check_output(["make", "-n", "-B", "-C", os.path.dirname(MAKEFILE), "../libmcfcsplit.so"]).decode()
+def test_the_library_is_built_from_its_own_unit_and_holds_its_own_kernels():
+    assert L.print_libraries()["libmcfcsplit.so"] == ["fc_split.o", "error.o"]
+    out = L.make("-n", "-B", "../libmcfcsplit.so")
     assert "fc_split.hip" in out and "error.hip" in out and "-o ../libmcfcsplit.so" in out and "fc_stack.hip" not in out
-
-
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(kc.INVENTORY_FC_SPLIT)
-    out = subprocess.check_output(["nm", "-C", fsl.LIB_PATH]).decode()
-    built = {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-    assert built == set(inv) == {"fcs_project_kernel", "fcs_transpose_kernel", "fcs_split_weights_kernel", "fcs_stack_kernel"}
-    others = set()                   # a library of its own: no kernel name of the other inventories, which stay as they are
-    for path in (kc.INVENTORY, kc.INVENTORY_TRAIN_SLOW, kc.INVENTORY_TRAIN_MB, kc.INVENTORY_TRAIN_MB_SLOW, kc.INVENTORY_EVAL,
-                 kc.INVENTORY_TRAIN_DEPTH):
-        others |= set(kc.read_inventory(path))
-    assert not built & others
-    assert "INVENTORY_FC_SPLIT]" in open(os.path.join(ROOT, "scripts", "kernel_coverage.py")).read()    # among --inventory's defaults
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(ROOT, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)
+    assert "fc_split" not in L.make("-n", "-B", "../libmcadcensus.so")               # libmcadcensus.so keeps its kernel set
+    assert L.built_kernels(fsl.LIB_PATH) == {"fcs_project_kernel", "fcs_transpose_kernel", "fcs_split_weights_kernel", "fcs_stack_kernel"}
 
 
 # ---- the flag ------------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,6 @@ import itertools
 import os
 import random
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import libraries as L  # noqa: E402
 from mc_cnn_amd import _eval_lib as ev  # noqa: E402
 from mc_cnn_amd import hs  # noqa: E402
 from mc_cnn_amd.params import TABLES, McParams  # noqa: E402
@@ -222,15 +222,11 @@ def test_parse_defaults():
 
 # ---- libmceval.so ----------------------------------------------------------------------------------------------------------------
 def test_eval_lib_loads_without_a_gpu_and_exports_the_headers_symbols():
-    lib = ev.load()
-    assert lib.mc_eval_version() == ev.ABI_VERSION == 1
-    header = open(os.path.join(ROOT, "include", "mc_eval.h")).read()
-    declared = set(re.findall(r"\b(mc_eval_\w+)\s*\(", header))
-    assert declared == set(ev.SYMBOLS) == {"mc_eval_version", "mc_eval_last_error", "mc_eval_error"}
-    assert int(re.search(r"#define MC_EVAL_ABI_VERSION (\d+)", header).group(1)) == ev.ABI_VERSION
-    out = subprocess.check_output(["nm", "-D", "--defined-only", ev.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert {s for s in exported if s.startswith("mc_")} == declared
+    """what only libmceval.so has; tests/test_libraries_host.py holds it to the contract of every library"""
+    assert L.exported_abi(ev.LIB_PATH) == {"mc_eval_version", "mc_eval_last_error", "mc_eval_error"}
+    assert ev.load().mc_eval_version() == ev.ABI_VERSION == 1
+    assert L.built_kernels(ev.LIB_PATH) == {"eval_error_kernel"}
+    assert L.print_libraries()["libmceval.so"] == ["eval.o", "error.o"]
 
 
 def test_mc_eval_error_refusals_write_nothing():
@@ -254,31 +250,3 @@ def test_mc_eval_error_refusals_write_nothing():
         assert counts.tolist() == [7, 8, 9, 10], what
     with pytest.raises(ev.EvalError, match="stride"):
         ev.check(call(pred_ld=1), "mc_eval_error")
-
-
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(kc.INVENTORY_EVAL)
-    out = subprocess.check_output(["nm", "-C", ev.LIB_PATH]).decode()
-    built = {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-    assert built == set(inv) == {"eval_error_kernel"}
-    for other in (kc.INVENTORY, kc.INVENTORY_TRAIN_SLOW, kc.INVENTORY_TRAIN_MB, kc.INVENTORY_TRAIN_MB_SLOW):
-        assert not built & set(kc.read_inventory(other))
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(ROOT, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)
-
-
-def test_the_makefile_builds_six_libraries():
-    mk = open(os.path.join(ROOT, "mc-cnn_amd", "csrc", "Makefile")).read()
-    all_line = re.search(r"^all:(.*)$", mk, re.M).group(1).split()
-    assert len(all_line) == 6 and "$(EVAL_LIB)" in all_line
-    assert re.search(r"^\$\(EVAL_LIB\): \$\(EVAL_OBJS\) error\.o$", mk, re.M)
-    for name in ("libmcadcensus.so", "libmctrain.so", "libmctrainslow.so", "libmctrainmb.so", "libmctrainmbslow.so", "libmceval.so"):
-        assert os.path.exists(os.path.join(ROOT, "mc-cnn_amd", name)), name

@@ -13,6 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import libraries as L  # noqa: E402
 import test_lua_shim as shim  # noqa: E402  (its header / cdef parsers)
 from mc_cnn_amd import _ops_lib as ol  # noqa: E402
 
@@ -35,20 +36,14 @@ def ctype_of(decl, is_return=False):
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------
 def test_library_loads_without_a_gpu_and_exports_the_headers_symbols():
-    lib = ol.load()
+    """what only libmcops.so has; tests/test_libraries_host.py holds it to the contract of every library"""
     text = open(HEADER).read()
-    assert lib.mc_ops_version() == ol.ABI_VERSION == int(re.search(r"#define MC_OPS_ABI_VERSION (\d+)", text).group(1)) == 1
-    decls = header_decls()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", ol.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] in "TtDBW" and
-                line.split()[-1].startswith("mc_")}
-    assert exported == set(decls) == set(ol.SYMBOLS) and len(exported) == 9
+    assert ol.load().mc_ops_version() == ol.ABI_VERSION == 1
+    exported = L.exported_abi(ol.LIB_PATH)
+    assert exported == set(header_decls()) == set(ol.SYMBOLS) and len(exported) == 9
     for name, value in (("MAX_C", ol.MAX_C), ("MAX_W", ol.MAX_W), ("SUBSET_IMAGES", ol.SUBSET_IMAGES)):
         assert re.search(r"#define MC_OPS_%s %d\b" % (name, value), text), name
     assert (ol.MAX_C, ol.MAX_W, ol.SUBSET_IMAGES, ol.EINVAL) == (128, 8192, 200, -22)
-    # nothing but the ABI leaves the library
-    syms = [l.split()[-1] for l in out.splitlines() if " T " in l]
-    assert syms and all(s.startswith("mc_") for s in syms), syms
 
 
 def test_ctypes_signatures_equal_the_headers_prototypes():
@@ -59,15 +54,13 @@ def test_ctypes_signatures_equal_the_headers_prototypes():
         assert ol.SIGNATURES[name] == (ctype_of(ret, True), argtypes), (name, d)
 
 
-def test_the_makefile_builds_an_eleventh_library_on_a_line_of_its_own():
-    mk = open(os.path.join(ROOT, "mc-cnn_amd", "csrc", "Makefile")).read()
-    alls = re.findall(r"^all:(.*)$", mk, re.M)
-    assert len(alls[0].split()) == 6 and alls[-1].split() == ["$(OPS_LIB)"] and len(alls) == 6
-    assert re.search(r"^\$\(OPS_LIB\): \$\(OPS_OBJS\) error\.o$", mk, re.M) and "../../include/mc_ops.h" in re.search(r"^HDRS = (.*\\\n)*.*$", mk, re.M).group(0)
-    clean = mk[mk.index("clean:"):]
-    assert "$(OPS_OBJS)" in clean and "$(OPS_LIB)" in clean
-    for var in ("SRCS", "TRAIN_OBJS"):                        # the older kernel sets stay as they are
-        assert "ops" not in re.search(r"^%s = (.*)$" % var, mk, re.M).group(1)
+def test_the_library_is_built_from_its_own_units_and_holds_its_own_kernels():
+    built = L.print_libraries()
+    assert built["libmcops.so"] == ["ops.o", "ops_normalize.o", "error.o"]
+    for older in ("libmcadcensus.so", "libmctrain.so"):       # the older kernel sets stay as they are
+        assert not any("ops" in obj for obj in built[older])
+    assert L.built_kernels(ol.LIB_PATH) == {"normalize_backward_kernel", "margin2_kernel<1>", "margin2_kernel<2>", "remove_nonvisible_kernel",
+                                            "remove_occluded_kernel", "remove_white_kernel"}
 
 
 def test_argument_checks_return_einval_with_a_message_before_any_launch():
@@ -206,32 +199,6 @@ def test_python_table_has_the_seven_names_with_the_references_arguments(mc):
     assert set(want) == set(SEVEN)
     for fn, args in want.items():
         assert list(inspect.signature(getattr(mc.adcensus, fn)).parameters) == args, fn
-
-
-# ---- the kernel inventory ----------------------------------------------------------------------------------------------------------
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(kc.INVENTORY_OPS)
-    out = subprocess.check_output(["nm", "-C", ol.LIB_PATH]).decode()
-    built = {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-    want = {"normalize_backward_kernel", "margin2_kernel<1>", "margin2_kernel<2>", "remove_nonvisible_kernel", "remove_occluded_kernel",
-            "remove_white_kernel"}
-    assert built == set(inv) == want
-    others = set()                   # a library of its own: no kernel name of the other inventories, which stay as they are
-    for path in (kc.INVENTORY, kc.INVENTORY_TRAIN_SLOW, kc.INVENTORY_TRAIN_MB, kc.INVENTORY_TRAIN_MB_SLOW, kc.INVENTORY_EVAL,
-                 kc.INVENTORY_TRAIN_DEPTH, kc.INVENTORY_FC_SPLIT, kc.INVENTORY_CONV_SPLIT, kc.INVENTORY_TRAIN_SLOW_DEPTH):
-        others |= set(kc.read_inventory(path))
-    assert not built & others
-    assert "INVENTORY_OPS," in open(os.path.join(ROOT, "scripts", "kernel_coverage.py")).read()    # among --inventory's defaults
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(ROOT, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)
 
 
 # ---- the package without the library -----------------------------------------------------------------------------------------------

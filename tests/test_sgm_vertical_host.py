@@ -40,31 +40,16 @@ def test_vertical_launches_slots_fallbacks_and_error_paths(tmp_path):
     assert n_checked >= 1000 and n_failed == 0, (n_checked, n_failed)
 
 
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
+def test_the_recompute_kernels_live_in_their_own_library_beside_the_one_that_needs_it():
     """libmcsgmrecompute.so holds the recomputing kernels and nothing else; libmcadcensus.so, which links against it, holds none of them, so
     its own inventory stays as it is"""
-    import importlib.util
-    root = os.path.join(HERE, "..")
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(root, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(kc.INVENTORY_SGM_RECOMPUTE)
-
-    def kernels(lib):
-        out = subprocess.check_output(["nm", "-C", os.path.join(root, "mc-cnn_amd", lib)]).decode()
-        return {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-
+    import libraries as L
+    adcensus = L.path("libmcadcensus.so")
     want = {"sgm_pass_kernel<2, 4, 4, false, true, 16, false, false>", "sgm_updown_kernel<8, true>", "sgm_updown_kernel<8, false>"}
-    assert kernels("libmcsgmrecompute.so") == set(inv) == want
-    assert not want & kernels("libmcadcensus.so") and not want & set(kc.read_inventory(kc.INVENTORY))
-    needed = subprocess.check_output(["readelf", "-d", os.path.join(root, "mc-cnn_amd", "libmcadcensus.so")]).decode()
+    assert L.built_kernels(L.path("libmcsgmrecompute.so")) == want
+    assert not want & L.built_kernels(adcensus) and not want & set(L.read_inventory("kernel_inventory.txt"))
+    needed = subprocess.check_output(["readelf", "-d", adcensus]).decode()
     assert "libmcsgmrecompute.so" in needed and "$ORIGIN" in needed   # found beside the library that needs it
     # sgm_sweeps_ck is declared weak (the lanes' host check links predict.hip without sgm.hip): the library itself must define it
-    syms = subprocess.check_output(["nm", "-C", "--defined-only", os.path.join(root, "mc-cnn_amd", "libmcadcensus.so")]).decode()
+    syms = subprocess.check_output(["nm", "-C", "--defined-only", adcensus]).decode()
     assert re.search(r"^[0-9a-f]+ [TtWw] mc::sgm_sweeps_ck\(", syms, re.M)
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(root, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)

@@ -3,7 +3,6 @@ and argument checks, the parameter layout per depth, the flags -l1 / -fm / -ks w
 of train_depth.train, and hs.py's -l1."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import libraries as L  # noqa: E402
 import train_fast_oracle as do  # noqa: E402
 from mc_cnn_amd import _train_depth_lib as tdl  # noqa: E402
 from mc_cnn_amd import hs, train, train_depth, train_mb  # noqa: E402
@@ -24,18 +24,17 @@ HEADER = os.path.join(ROOT, "include", "mc_train_depth.h")
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------
 def test_library_loads_without_a_gpu_and_exports_the_headers_symbols():
-    lib = tdl.load()
+    """what only libmctraindepth.so has; tests/test_libraries_host.py holds it to the contract of every library"""
     text = open(HEADER).read()
-    assert lib.mc_train_depth_version() == tdl.ABI_VERSION == int(re.search(r"#define MC_TRAIN_DEPTH_ABI_VERSION (\d+)", text).group(1))
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(mc_train_depth_\w+)\s*\(", code))
-    out = subprocess.check_output(["nm", "-D", "--defined-only", tdl.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] in "TtDBW" and
-                line.split()[-1].startswith("mc_")}
-    assert exported == declared == set(tdl.SYMBOLS) and len(exported) == 10
+    assert len(L.exported_abi(tdl.LIB_PATH)) == 10
     for name, value in (("MIN_L1", tdl.MIN_L1), ("MAX_L1", tdl.MAX_L1), ("FM", tdl.FM), ("NPRM", tdl.NPRM), ("MAX_PAIRS", tdl.MAX_PAIRS)):
         assert re.search(r"#define MC_TRAIN_DEPTH_%s %d\b" % (name, value), text), name
     assert (tdl.MIN_L1, tdl.MAX_L1, tdl.FM, tdl.NPRM, tdl.MAX_PAIRS, tdl.EINVAL) == (1, 5, 64, 18, 1024, -22)
+    want = {"train_depth_sgd_kernel"}
+    for l1 in TABLE:
+        want |= {"train_depth_sample_kernel<%d>" % l1, "train_depth_mb_sample_kernel<%d>" % l1, "train_depth_mb_step_kernel<%d>" % l1,
+                 "train_depth_step_kernel<%d, true>" % l1, "train_depth_step_kernel<%d, false>" % l1}
+    assert L.built_kernels(tdl.LIB_PATH) == want and len(want) == 26
 
 
 def test_sizes_equal_the_headers_table_and_are_zero_outside_it():
@@ -115,31 +114,6 @@ def test_argument_checks_return_einval_with_a_message_before_any_launch():
     assert step(l1=6) == tdl.EINVAL and "254464 bytes in LDS" in tdl.last_error()      # why six layers are refused
     with pytest.raises(tdl.TrainDepthError, match="n_pairs"):
         tdl.check(step(n=0), "mc_train_depth_step_batch")
-
-
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(kc.INVENTORY_TRAIN_DEPTH)
-    out = subprocess.check_output(["nm", "-C", tdl.LIB_PATH]).decode()
-    built = {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-    want = {"train_depth_sgd_kernel"}
-    for l1 in TABLE:
-        want |= {"train_depth_sample_kernel<%d>" % l1, "train_depth_mb_sample_kernel<%d>" % l1, "train_depth_mb_step_kernel<%d>" % l1,
-                 "train_depth_step_kernel<%d, true>" % l1, "train_depth_step_kernel<%d, false>" % l1}
-    assert built == set(inv) == want and len(want) == 26
-    others = set()                   # a library of its own: no kernel name of the other inventories, which stay as they are
-    for path in (kc.INVENTORY, kc.INVENTORY_TRAIN_SLOW, kc.INVENTORY_TRAIN_MB, kc.INVENTORY_TRAIN_MB_SLOW, kc.INVENTORY_EVAL):
-        others |= set(kc.read_inventory(path))
-    assert not built & others
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(ROOT, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)
 
 
 # ---- the parameter layout --------------------------------------------------------------------------------------------------------

@@ -3,7 +3,6 @@ routing, the loader of a ragged data.mb.* directory and its plane store, the sou
 parameter layout and the saved net, and libmctrainmb.so's symbols and argument checks."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import libraries as L  # noqa: E402
 import train_mb_oracle as mo  # noqa: E402
 from mc_cnn_amd import binio  # noqa: E402
 from mc_cnn_amd import main as mcmain  # noqa: E402
@@ -271,44 +271,15 @@ def test_saved_net_round_trips_into_the_readers(tmp_path):
 
 
 # ---- the library -------------------------------------------------------------------------------------------------------------
-def header_symbols():
-    text = open(os.path.join(ROOT, "include", "mc_train_mb.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b(mc_train_mb_\w+)\s*\(", text))
-
-
 def test_library_loads_without_a_gpu_and_exports_the_headers_symbols():
-    lib = tm.tml.load()
-    assert lib.mc_train_mb_version() == 1
-    out = subprocess.check_output(["nm", "-D", "--defined-only", tm.tml.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] in "TtDBW" and
-                line.split()[-1].startswith("mc_")}
-    assert exported == header_symbols() == set(tm.tml.SYMBOLS) and len(exported) == 6
+    """what only libmctrainmb.so has; tests/test_libraries_host.py holds it to the contract of every library"""
+    assert tm.tml.load().mc_train_mb_version() == 1 and len(L.exported_abi(tm.tml.LIB_PATH)) == 6
     text = open(os.path.join(ROOT, "include", "mc_train_mb.h")).read()
     for name, value in (("NPARAMS", tm.tml.NPARAMS), ("MAX_PAIRS", tm.tml.MAX_PAIRS), ("FM", tm.tml.FM), ("L1", tm.tml.L1), ("WS", tm.tml.WS),
                         ("NPRM", tm.tml.NPRM), ("ABI_VERSION", tm.tml.ABI_VERSION)):
         assert re.search(r"#define MC_TRAIN_MB_%s %d\b" % (name, value), text), name
     assert (tm.tml.WS, tm.tml.L1, tm.tml.FM, tm.tml.NPRM) == (11, 5, 64, 18) and tm.tml.MAX_PAIRS >= 64
-
-
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(kc.INVENTORY_TRAIN_MB)
-    out = subprocess.check_output(["nm", "-C", tm.tml.LIB_PATH]).decode()
-    built = {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-    assert built == set(inv) == {"train_mb_sample_kernel", "train_mb_step_kernel<true>", "train_mb_step_kernel<false>", "train_mb_sgd_kernel"}
-    # a library of its own: no kernel name of the other inventories, which stay as they are
-    others = set(kc.read_inventory(kc.INVENTORY)) | set(kc.read_inventory(kc.INVENTORY_TRAIN_SLOW))
-    assert not built & others
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(ROOT, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)
+    assert L.built_kernels(tm.tml.LIB_PATH) == {"train_mb_sample_kernel", "train_mb_step_kernel<true>", "train_mb_step_kernel<false>", "train_mb_sgd_kernel"}
 
 
 def test_workspace_bytes():

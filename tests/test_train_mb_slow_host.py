@@ -4,7 +4,6 @@ symbols, constants, workspace sizes, argument checks and kernel inventory, and t
 recording stand-in for its Trainer."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import libraries as L  # noqa: E402
 import train_mb_slow_oracle as so  # noqa: E402
 from mc_cnn_amd import main as mcmain  # noqa: E402
 from mc_cnn_amd import train_mb as tm  # noqa: E402
@@ -180,18 +180,16 @@ def test_oracle_forward_pairs_left_with_positive_then_negative():
 HEADER = os.path.join(ROOT, "include", "mc_train_mb_slow.h")
 
 
-def header_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(mc_train_mb_slow_\w+)\s*\(", text))
-
-
 def test_library_loads_without_a_gpu_and_exports_the_headers_symbols():
-    lib = tms.tmsl.load()
-    assert lib.mc_train_mb_slow_version() == 1
-    out = subprocess.check_output(["nm", "-D", "--defined-only", tms.tmsl.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] in "TtDBW" and
-                line.split()[-1].startswith("mc_")}
-    assert exported == header_symbols() == set(tms.tmsl.SYMBOLS) and len(exported) == 5     # no sampler entry point
+    """what only libmctrainmbslow.so has; tests/test_libraries_host.py holds it to the contract of every library"""
+    assert tms.tmsl.load().mc_train_mb_slow_version() == 1 and len(L.exported_abi(tms.tmsl.LIB_PATH)) == 5     # no sampler entry point
+    built = L.built_kernels(tms.tmsl.LIB_PATH)
+    # the FC kernels are the KITTI accurate net's (one header, compiled into both libraries); the rest is this library's own,
+    # and there is no sampler kernel: libmctrainmb.so's draws the same patches
+    assert built == L.SHARED_KERNELS | {"mb_tower_forward_kernel<true>", "mb_tower_forward_kernel<false>", "mb_tower_backward_kernel", "mb_slow_sgd_kernel"}
+    assert len(built) == 8 and built & set(L.read_inventory("kernel_inventory_train_slow.txt")) == L.SHARED_KERNELS
+    assert L.SHARED_KERNELS == {"fc_forward_kernel", "fc_head_kernel", "fc_backward_kernel<true>", "fc_backward_kernel<false>"}
+    assert not any("sample" in k for k in built)
 
 
 def test_loader_constants_equal_the_headers_defines():
@@ -251,31 +249,6 @@ def test_argument_checks_return_einval_with_a_message_before_any_launch():
         assert word in tms.tmsl.last_error(), (what, tms.tmsl.last_error())
     with pytest.raises(tms.tmsl.TrainMbSlowError, match="n_pairs"):
         tms.tmsl.check(step(n=0), "mc_train_mb_slow_step_batch")
-
-
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(kc.INVENTORY_TRAIN_MB_SLOW)
-    out = subprocess.check_output(["nm", "-C", tms.tmsl.LIB_PATH]).decode()
-    built = {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-    assert built == set(inv) == {"mb_tower_forward_kernel<true>", "mb_tower_forward_kernel<false>", "mb_tower_backward_kernel",
-                                 "fc_forward_kernel", "fc_head_kernel", "fc_backward_kernel<true>", "fc_backward_kernel<false>",
-                                 "mb_slow_sgd_kernel"}
-    # the FC kernels are the KITTI accurate net's (one header, compiled into both libraries); the rest is this library's own,
-    # and there is no sampler kernel: libmctrainmb.so's draws the same patches
-    shared = built & set(kc.read_inventory(kc.INVENTORY_TRAIN_SLOW))
-    assert shared == {"fc_forward_kernel", "fc_head_kernel", "fc_backward_kernel<true>", "fc_backward_kernel<false>"}
-    assert not built & (set(kc.read_inventory(kc.INVENTORY)) | set(kc.read_inventory(kc.INVENTORY_TRAIN_MB)))
-    assert not any("sample" in k for k in built)
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(ROOT, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)
 
 
 # ---- the host loop -------------------------------------------------------------------------------------------------------

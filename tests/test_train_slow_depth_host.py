@@ -3,7 +3,6 @@ sizes and argument checks, the parameter layout per depth, the flags -l2 / -nh2 
 of train_slow_depth.train, load_fc's and hs.py's -l2, and the depth a saved .t7 carries."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import libraries as L  # noqa: E402
 import train_slow_oracle as so  # noqa: E402
 from mc_cnn_amd import _train_slow_depth_lib as tsdl  # noqa: E402
 from mc_cnn_amd import hs, train_mb, train_mb_slow, train_slow, train_slow_depth  # noqa: E402
@@ -25,21 +25,20 @@ DEPTHS = range(1, 8)
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------
 def test_library_loads_without_a_gpu_and_exports_the_headers_symbols():
-    lib = tsdl.load()
+    """what only libmctrainslowdepth.so has; tests/test_libraries_host.py holds it to the contract of every library"""
     text = open(HEADER).read()
-    assert lib.mc_train_slow_depth_version() == tsdl.ABI_VERSION == int(re.search(r"#define MC_TRAIN_SLOW_DEPTH_ABI_VERSION (\d+)", text).group(1))
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(mc_train_slow_depth_\w+)\s*\(", code))
-    out = subprocess.check_output(["nm", "-D", "--defined-only", tsdl.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] in "TtDBW" and
-                line.split()[-1].startswith("mc_")}
-    assert exported == declared == set(tsdl.SYMBOLS) and len(exported) == 7
+    assert len(L.exported_abi(tsdl.LIB_PATH)) == 7
     for name, value in (("KITTI", tsdl.KITTI), ("MB", tsdl.MB), ("MIN_L2", tsdl.MIN_L2), ("MAX_L2", tsdl.MAX_L2), ("NH2", tsdl.NH2), ("NPRM", tsdl.NPRM),
                         ("NFC1", tsdl.NFC1), ("NFC_STEP", tsdl.NFC_STEP), ("MAX_PAIRS", tsdl.MAX_PAIRS[tsdl.KITTI]),
                         ("MB_MAX_PAIRS", tsdl.MAX_PAIRS[tsdl.MB])):
         assert re.search(r"#define MC_TRAIN_SLOW_DEPTH_%s %d\b" % (name, value), text), name
     assert (tsdl.MIN_L2, tsdl.MAX_L2, tsdl.NH2, tsdl.NPRM, tsdl.EINVAL) == (1, 7, 384, 18, -22)
     assert tsdl.MAX_PAIRS == {tsdl.KITTI: train_slow.tsl.MAX_PAIRS, tsdl.MB: train_mb_slow.tmsl.MAX_PAIRS} == {0: 1024, 1: 256}
+    # train_slow_fc.h's four, the towers once per tower, never once per l2, and one update kernel
+    want = L.SHARED_KERNELS | {"depth_tower_forward_kernel<true>", "depth_tower_forward_kernel<false>", "depth_mb_tower_forward_kernel<true>",
+                               "depth_mb_tower_forward_kernel<false>", "depth_tower_backward_kernel<KittiTower>",
+                               "depth_tower_backward_kernel<MbTower>", "train_slow_depth_sgd_kernel"}
+    assert L.built_kernels(tsdl.LIB_PATH) == want and len(want) == 11
 
 
 def test_sizes_equal_the_headers_table_and_the_parents_constants():
@@ -127,33 +126,6 @@ def test_argument_checks_return_einval_with_a_message_before_any_launch():
     assert step(l2=8) == tsdl.EINVAL and "mc_fc_stack takes 8 layers" in tsdl.last_error()
     with pytest.raises(tsdl.TrainSlowDepthError, match="n_pairs"):
         tsdl.check(step(n=0), "mc_train_slow_depth_step_batch")
-
-
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(kc.INVENTORY_TRAIN_SLOW_DEPTH)
-    out = subprocess.check_output(["nm", "-C", tsdl.LIB_PATH]).decode()
-    built = {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-    fc = {"fc_forward_kernel", "fc_head_kernel", "fc_backward_kernel<true>", "fc_backward_kernel<false>"}
-    want = fc | {"depth_tower_forward_kernel<true>", "depth_tower_forward_kernel<false>", "depth_mb_tower_forward_kernel<true>",
-                 "depth_mb_tower_forward_kernel<false>", "depth_tower_backward_kernel<KittiTower>", "depth_tower_backward_kernel<MbTower>",
-                 "train_slow_depth_sgd_kernel"}
-    assert built == set(inv) == want and len(want) == 11           # the towers once per tower, never once per l2; one update kernel
-    others = set()                   # a library of its own: beyond train_slow_fc.h's four, no kernel name of the other inventories
-    for path in (kc.INVENTORY, kc.INVENTORY_TRAIN_SLOW, kc.INVENTORY_TRAIN_MB, kc.INVENTORY_TRAIN_MB_SLOW, kc.INVENTORY_EVAL, kc.INVENTORY_TRAIN_DEPTH,
-                 kc.INVENTORY_FC_SPLIT, kc.INVENTORY_CONV_SPLIT):
-        others |= set(kc.read_inventory(path))
-    assert built & others == fc
-    assert "INVENTORY_TRAIN_SLOW_DEPTH," in open(os.path.join(ROOT, "scripts", "kernel_coverage.py")).read()    # among --inventory's defaults
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(ROOT, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)
 
 
 # ---- the parameter layout --------------------------------------------------------------------------------------------------------

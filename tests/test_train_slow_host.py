@@ -3,7 +3,6 @@ flags, the flat parameter layout and the saved net, the criterion's oracle, libm
 and kernel inventory, and the host loop of `train_slow.train` with a recording stand-in for its Trainer."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import libraries as L  # noqa: E402
 import train_slow_oracle as so  # noqa: E402
 from mc_cnn_amd import main as mcmain  # noqa: E402
 from mc_cnn_amd import train_slow as ts  # noqa: E402
@@ -159,19 +159,9 @@ def test_oracle_forward_pairs_left_with_positive_then_negative():
 
 
 # ---- the library -------------------------------------------------------------------------------------------------------
-def header_symbols():
-    text = open(os.path.join(ROOT, "include", "mc_train_slow.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b(mc_train_slow_\w+)\s*\(", text))
-
-
 def test_library_loads_without_a_gpu_and_exports_the_headers_symbols():
-    lib = ts.tsl.load()
-    assert lib.mc_train_slow_version() == 1
-    out = subprocess.check_output(["nm", "-D", "--defined-only", ts.tsl.LIB_PATH]).decode()
-    exported = {line.split()[-1] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] in "TtDBW" and
-                line.split()[-1].startswith("mc_")}
-    assert exported == header_symbols() == set(ts.tsl.SYMBOLS)
+    """what only libmctrainslow.so has; tests/test_libraries_host.py holds it to the contract of every library"""
+    assert ts.tsl.load().mc_train_slow_version() == 1
     text = open(os.path.join(ROOT, "include", "mc_train_slow.h")).read()
     for name, value in (("NPARAMS", ts.tsl.NPARAMS), ("NCONV", ts.tsl.NCONV), ("NFC", ts.tsl.NFC), ("MAX_PAIRS", ts.tsl.MAX_PAIRS),
                         ("FM", ts.tsl.FM), ("NH2", ts.tsl.NH2), ("NPRM", ts.tsl.NPRM), ("ABI_VERSION", ts.tsl.ABI_VERSION)):
@@ -223,24 +213,10 @@ def test_argument_checks_return_einval_with_a_message_before_any_launch():
         ts.tsl.check(step(n=0), "mc_train_slow_step_batch")
 
 
-def test_kernel_inventory_lists_exactly_the_librarys_kernels():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "scripts", "kernel_coverage.py"))
-    kc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kc)
-    inv = kc.read_inventory(os.path.join(ROOT, "tests", "kernel_inventory_train_slow.txt"))
-    out = subprocess.check_output(["nm", "-C", ts.tsl.LIB_PATH]).decode()
-    built = {kc.normalise(re.sub(r"^[0-9a-fA-F]*\s+[a-zA-Z]\s+", "", line)) for line in out.splitlines() if "__device_stub__" in line}
-    assert built and set(inv) == built, (sorted(built - set(inv)), sorted(set(inv) - built))
+def test_the_library_has_no_sampler_kernel_of_its_own():
     from mc_cnn_amd import _train_lib
-    others = subprocess.check_output(["nm", "-C", _train_lib.LIB_PATH]).decode()
-    assert "train_sample_kernel" in others and not any("sample_kernel" in k for k in built)   # no sampler entry of its own
-    for name, tests in inv.items():
-        assert tests, "%s: no test named" % name
-        for t in tests:
-            path, _, func = t.partition("::")
-            src = open(os.path.join(ROOT, path)).read()
-            assert func and re.search(r"^def %s\(" % re.escape(func), src, re.M), "%s: no test %s" % (name, t)
+    assert "train_sample_kernel" in L.built_kernels(_train_lib.LIB_PATH)
+    assert not any("sample_kernel" in k for k in L.built_kernels(ts.tsl.LIB_PATH))
 
 
 # ---- the host loop -------------------------------------------------------------------------------------------------------

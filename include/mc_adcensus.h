@@ -39,7 +39,7 @@ extern "C" {
 
 #define MC_ABI_VERSION 8
 #define MC_EINVAL (-22)
-#define MC_SGM_MAX_D 512   /* reference: __shared__ float[400], adcensus.cu:574 */
+#define MC_SGM_MAX_D 1024  /* 64 lanes x 16 values per lane in the line walk; the reference stops at __shared__ float[400], adcensus.cu:574 */
 #define MC_JOIN_MAX_C 128  /* reference: float L_cache[128], adcensus.cu:1460-1461 */
 
 /* adcensus.version (adcensus.cu funcs[]) analogue. */
@@ -124,14 +124,15 @@ int mc_cbca_ws(const float *x0c, const float *x1c, const float *vol_in, float *v
 /* ---- semiglobal matching ------------------------------------------------ */
 
 /* Bytes of scratch mc_sgm2 needs in `tmp` (edge-class maps; the reference's
- * tmp (W,D) line state lives in registers here). */
+ * tmp (W,D) line state lives in registers here).  One size for every D <= 512,
+ * a larger one for D in 513..MC_SGM_MAX_D (wider rows in the maps). */
 size_t mc_sgm2_tmp_bytes(int H, int W, int D);
 
 /* adcensus.sgm2(x0, x1, input, output, tmp, pi1, pi2, tau_so, alpha1, sgm_q1,
  * sgm_q2, direction), adcensus.cu:620-697 (kernels 535-618).  x0,x1: (H,W);
  * in_hwd/out_hwd: (H,W,D); the four directional costs are ADDED to out_hwd in
  * the reference's order (right, left, down, up), so the caller zeroes it first
- * (main.lua:1014).  D <= MC_SGM_MAX_D.  `tmp` must hold mc_sgm2_tmp_bytes();
+ * (main.lua:1014).  D <= MC_SGM_MAX_D (1024).  `tmp` must hold mc_sgm2_tmp_bytes(H, W, D) for this D;
  * pass tmp_bytes so that an undersized buffer is rejected, not overrun.
  * Contract: NaNs in a pixel's cost vector form a (possibly empty) tail in d
  * and d=0 is finite -- true for every volume the pipeline produces. */

@@ -196,10 +196,7 @@ def sgm2(x0, x1, input, output, tmp, pi1, pi2, tau_so, alpha1, sgm_q1, sgm_q2, d
     if isinstance(tmp, torch.Tensor) and tmp.is_cuda and tmp.is_contiguous() and tmp.numel() * tmp.element_size() >= need:
         scratch = tmp
     else:
-        key = (input.device.index, need)
-        scratch = _scratch.get(key)
-        if scratch is None:
-            scratch = _scratch[key] = torch.empty(need, dtype=torch.uint8, device=input.device)
+        scratch = _scratch_for(input.device, need)   # (the size follows D above 512; one area per stream, like every other operator's)
     check(lib.mc_sgm2(_p(x0), _p(x1), _p(input), _p(output), scratch.data_ptr(), scratch.numel() * scratch.element_size(),
                       H, W, D, float(pi1), float(pi2), float(tau_so), float(alpha1), float(sgm_q1), float(sgm_q2),
                       int(direction), _stream()), "sgm2")

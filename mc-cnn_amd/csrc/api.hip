@@ -271,9 +271,8 @@ int mc_sgm2_contract_violations(const float *in_hwd, int H, int W, int D, unsign
 
 size_t mc_sgm2_tmp_bytes(int H, int W, int D)
 {
-	(void)D;
 	if (H < 1 || W < 1) return 0;
-	return sgm_maps_bytes(H, W);
+	return sgm_maps_bytes_d(H, W, D);   // one size for every D <= 512, a larger one above (the window rows' pad)
 }
 
 int mc_sgm2(const float *x0, const float *x1, const float *in_hwd, float *out_hwd, void *tmp, size_t tmp_bytes, int H, int W,
@@ -283,10 +282,10 @@ int mc_sgm2(const float *x0, const float *x1, const float *in_hwd, float *out_hw
 	MC_REQUIRE(dims_ok(D, H, W), "mc_sgm2: bad dims");
 	MC_REQUIRE(D <= MC_SGM_MAX_D, "mc_sgm2: D=%d exceeds %d", D, MC_SGM_MAX_D);
 	MC_REQUIRE_DIRECTION("mc_sgm2", direction);
-	MC_REQUIRE(tmp_bytes >= sgm_maps_bytes(H, W), "mc_sgm2: tmp holds %zu bytes, needs %zu", tmp_bytes, sgm_maps_bytes(H, W));
+	MC_REQUIRE(tmp_bytes >= sgm_maps_bytes_d(H, W, D), "mc_sgm2: tmp holds %zu bytes, needs %zu", tmp_bytes, sgm_maps_bytes_d(H, W, D));
 	MC_REQUIRE(in_hwd != out_hwd, "mc_sgm2: input and output must differ");
 	hipStream_t st = as_stream(stream);
-	int rc = sgm_prep(x0, x1, tmp, H, W, tau_so, st);
+	int rc = sgm_prep_d(x0, x1, tmp, H, W, D, tau_so, st);
 	if (rc) return rc;
 	const float *Cv[2] = {in_hwd, in_hwd};
 	float *outv[2] = {out_hwd, out_hwd};

@@ -73,6 +73,11 @@ int fc_stack(const float *featL, const float *featR, int C, int H, int W, int D,
 // sgm.hip
 size_t sgm_maps_bytes(int H, int W);
 int sgm_prep(const float *x0, const float *x1, void *maps, int H, int W, float tau_so, hipStream_t st);
+// The maps of a call with D > 512 have wider window rows (sgm_line.h, SGM_PADW_WIDE): the two functions above are these at any D <= 512, where
+// size and layout are what they always were.  (predict.hip re-declares the two weak for itself: it asks them only where D > 512, and the host
+// check of the two lanes links it against stubs of the two functions above alone.)
+size_t sgm_maps_bytes_d(int H, int W, int D);
+int sgm_prep_d(const float *x0, const float *x1, void *maps, int H, int W, int D, float tau_so, hipStream_t st);
 int sgm_contract_violations(const float *vol, int H, int W, int D, unsigned *count, hipStream_t st);
 int sgm_sweeps(const float *const C[2], float *const out[2], float *const out2[2], float *const disp[2],
                const int direction[2], int nvol, int H, int W, int D, int ds, const void *maps, float pi1, float pi2,

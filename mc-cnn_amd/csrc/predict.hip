@@ -9,6 +9,11 @@
 
 namespace mc {
 
+// The maps of a range above 512 (sgm.hip).  Weak HERE only, like sgm_sweeps_ck: the host check of the two lanes links this unit against stubs of
+// sgm_maps_bytes / sgm_prep alone.  Without them a range above 512 is refused (predict_impl), never run on the narrower maps.
+size_t sgm_maps_bytes_d(int H, int W, int D) __attribute__((weak));
+int sgm_prep_d(const float *x0, const float *x1, void *maps, int H, int W, int D, float tau_so, hipStream_t st) __attribute__((weak));
+
 // gaussian(sigma), main.lua:528-540, double on the host.  mc_predict reads it from DEVICE memory, cached per (device, sigma): allocated and
 // uploaded synchronously at first use (complete before any stream can be given it) and never freed; it depends on the preset alone.
 void gaussian_fill(double sigma, float *k)
@@ -178,7 +183,8 @@ Plan make_plan(const mc_params *p, int D, int H, int W, void *base)
 
 	size_t off = 0;
 	auto take = [&](size_t bytes) { off += bytes; return base ? (char *)base + (off - bytes) : nullptr; };
-	pl.maps = take(align_up(sgm_maps_bytes(H, W), 256));
+	// (D > 512: the wider window rows of the VPL = 16 line walks; a program without sgm.hip gets the plain size here and predict_impl's refusal)
+	pl.maps = take(align_up((D > 512 && sgm_maps_bytes_d) ? sgm_maps_bytes_d(H, W, D) : sgm_maps_bytes(H, W), 256));
 	pl.x0c = (float *)take(align_up(8 * HW * sizeof(float), 256));
 	pl.x1c = base ? pl.x0c + 4 * HW : nullptr;
 	pl.packed = take(cbca_scratch_bytes(H, W));
@@ -225,6 +231,7 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	MC_REQUIRE(p && x0 && x1 && disp_out && workspace, "mc_predict: null argument");
 	MC_REQUIRE(dims_ok(D, H, W), "mc_predict: bad dims D=%d H=%d W=%d", D, H, W);
 	MC_REQUIRE(D <= MC_SGM_MAX_D, "mc_predict: D=%d exceeds %d", D, MC_SGM_MAX_D);
+	MC_REQUIRE(D <= 512 || (sgm_maps_bytes_d && sgm_prep_d), "mc_predict: D=%d needs the wide SGM maps, which this program does not link", D);
 	MC_REQUIRE((featL && featR && C >= 1) || (rawL && rawR), "mc_predict: need features or raw volumes");
 	MC_REQUIRE(p->cbca_i1 >= 0 && p->cbca_i2 >= 0 && p->sgm_i >= 0, "mc_predict: negative iteration count");
 	MC_REQUIRE(p->median_k % 2 == 1 && p->median_k <= 11, "mc_predict: median_k must be odd and <= 11");
@@ -255,7 +262,7 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	const bool use_cbca = (n_cbca1 + n_cbca2) > 0;
 	tm.mark(-1);
 
-	if (n_sgm > 0) RUN(sgm_prep(x0, x1, pl.maps, H, W, p->tau_so, st));
+	if (n_sgm > 0) RUN(D > 512 ? sgm_prep_d(x0, x1, pl.maps, H, W, D, p->tau_so, st) : sgm_prep(x0, x1, pl.maps, H, W, p->tau_so, st));
 	if (use_cbca) {  // main.lua:993-996: x0c from the LEFT image, x1c from the RIGHT, for both directions
 		RUN(cross(x0, pl.x0c, H, W, p->L1, p->tau1, st));
 		RUN(cross(x1, pl.x1c, H, W, p->L1, p->tau1, st));

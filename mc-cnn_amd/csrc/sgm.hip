@@ -28,6 +28,7 @@ namespace mc {
 __device__ __forceinline__ int cls_of(float v, float tau) { return v < tau ? 0 : (v > tau ? 2 : 1); }
 
 // r: 0 right (dx=1), 1 left (dx=-1), 2 down (dy=1), 3 up (dy=-1)  (adcensus.cu:541-565)
+// The pad of the window rows arrives as Wm = W + 2 * pad (sgm_padw: SGM_PADW for D <= 512, SGM_PADW_WIDE above).
 __global__ void __launch_bounds__(256) sgm_prep_kernel(const float *__restrict__ x0, const float *__restrict__ x1,
                                                        uint8_t *__restrict__ cls0, uint8_t *__restrict__ win,
                                                        int H, int W, int Wm, int64_t cls_plane, float tau_so)
@@ -51,7 +52,7 @@ __global__ void __launch_bounds__(256) sgm_prep_kernel(const float *__restrict__
 		}
 		cls0[(int64_t)r * cls_plane + (int64_t)y * W + x] = (uint8_t)c;
 	}
-	const int s = i - SGM_PADW;
+	const int s = i - ((Wm - W) >> 1);
 	unsigned asc = 0, desc = 0;
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {
@@ -101,20 +102,27 @@ int sgm_contract_violations(const float *vol, int H, int W, int D, unsigned *cou
 	return check_launch("sgm_contract");
 }
 
-// the maps sgm_prep writes and the sweeps read: cls0[4][plane] then win[2][4][H][Wm] (see SgmPassArgs); cls0 / win = byte offsets
+// the maps sgm_prep writes and the sweeps read: cls0[4][plane] then win[2][4][H][Wm] (see SgmPassArgs); cls0 / win = byte offsets.
+// The window rows' pad follows D (sgm_padw): every D <= 512 has the layout and the size it always had.
 struct SgmMaps { int Wm; size_t plane, cls0, win, bytes; };
-static SgmMaps sgm_maps(int H, int W)
+static SgmMaps sgm_maps(int H, int W, int D)
 {
-	const int Wm = W + 2 * SGM_PADW;
+	const int Wm = W + 2 * sgm_padw(D);
 	const size_t plane = ((size_t)H * W + 3 + 4) / 4 * 4;  // dword-aligned class planes (+4: the dword read may straddle)
 	return {Wm, plane, 0, 4 * plane, (4 * plane + (size_t)8 * H * Wm + 255) & ~(size_t)255};
 }
 
-size_t sgm_maps_bytes(int H, int W) { return sgm_maps(H, W).bytes; }
+size_t sgm_maps_bytes(int H, int W) { return sgm_maps(H, W, 1).bytes; }
+size_t sgm_maps_bytes_d(int H, int W, int D) { return sgm_maps(H, W, D).bytes; }
 
 int sgm_prep(const float *x0, const float *x1, void *maps, int H, int W, float tau_so, hipStream_t st)
 {
-	const SgmMaps m = sgm_maps(H, W);
+	return sgm_prep_d(x0, x1, maps, H, W, 1, tau_so, st);
+}
+
+int sgm_prep_d(const float *x0, const float *x1, void *maps, int H, int W, int D, float tau_so, hipStream_t st)
+{
+	const SgmMaps m = sgm_maps(H, W, D);
 	const int64_t total = (int64_t)4 * H * m.Wm;
 	hipLaunchKernelGGL(sgm_prep_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, x0, x1, (uint8_t *)maps + m.cls0, (uint8_t *)maps + m.win, H, W,
 	                   m.Wm, (int64_t)m.plane, tau_so);
@@ -145,8 +153,12 @@ static void launch_pass(const SgmPassArgs &A, bool vec, hipStream_t st)
 #define MC_SGM_GO_FAR(VPL_, VEC_, U_) \
 	hipLaunchKernelGGL((sgm_pass_kernel<DIRN, VPL_, MODE, ARGMIN, VEC_, U_, DUAL, true>), grid, block, 0, st, A)
 	// a volume of 2 GiB or more: 64-bit pixel addresses in every step (one prefetch depth only)
-	const bool far = (int64_t)A.H * A.W * A.ds * 4 >= ((int64_t)1 << 31);
-	if (!vec) {
+	const bool far = sgm_far(A.H, A.W, A.ds);
+	if (A.D > 512) {
+		// the walk at 16 values per lane, all its forms (per element, vector, each with and without FAR), lives in this kernel and picks its form
+		// itself (sgm_line_wide); (fused modes: sgm_sweeps has required vec)
+		MC_SGM_GO(8, true, 8);
+	} else if (!vec) {
 		if constexpr (SCALAR) {
 			if (far) { if (A.D <= 256) MC_SGM_GO_FAR(4, false, 4); else MC_SGM_GO_FAR(8, false, 2); }
 			else { if (A.D <= 256) MC_SGM_GO(4, false, 4); else MC_SGM_GO(8, false, 2); }
@@ -226,7 +238,7 @@ int sgm_sweeps_ck(const float *const C[2], float *const out[2], float *const out
 	A.nvol = nvol;
 	A.tri = (fused && tri) ? 1 : 0;
 	A.H = H; A.W = W; A.D = D; A.ds = ds;
-	const SgmMaps m = sgm_maps(H, W);
+	const SgmMaps m = sgm_maps(H, W, D);   // (the caller's maps are sgm_prep_d's for this D)
 	A.Wm = m.Wm;
 	A.cls0 = (const uint8_t *)maps + m.cls0;
 	A.cls_plane = (int64_t)m.plane;
@@ -237,11 +249,7 @@ int sgm_sweeps_ck(const float *const C[2], float *const out[2], float *const out
 	A.P1[2] = pi1 / (q1 * q2); A.P2[2] = pi2 / (q1 * q2);
 	for (int k = 0; k < 3; ++k) A.P1a[k] = A.P1[k] / alpha1;  // adcensus.cu:609,612
 
-	bool vec = (ds % 4 == 0);
-	for (int v = 0; v < nvol; ++v) {
-		vec = vec && ((uintptr_t)C[v] % 16 == 0) && ((uintptr_t)out[v] % 16 == 0);
-		if (out2) vec = vec && ((uintptr_t)out2[v] % 16 == 0);
-	}
+	const bool vec = sgm_vec(A);
 	const bool am = fused && disp && disp[0];
 	if (!fused) {
 		launch_pass<0, 1, false, false>(A, vec, st);
@@ -253,7 +261,7 @@ int sgm_sweeps_ck(const float *const C[2], float *const out[2], float *const out
 		MC_REQUIRE(out2 && vec, "sgm: the fused sweeps need the second direction's scratch and 16-byte aligned volumes with ds %% 4 == 0");
 		launch_pass<0, 0, false, true>(A, vec, st);
 		if (const int rc = check_launch("sgm_pass horizontal")) return rc;
-		const bool far = (int64_t)H * W * ds * 4 >= ((int64_t)1 << 31);
+		const bool far = sgm_far(H, W, ds);
 		bool slots = ck != nullptr;
 		for (int v = 0; v < nvol && slots; ++v) slots = ck[v] && (uintptr_t)ck[v] % 16 == 0;
 		if (slots && D <= 256 && !far && sgm_vertical() == 2) {

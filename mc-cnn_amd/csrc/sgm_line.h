@@ -13,6 +13,12 @@
 namespace mc {
 
 constexpr int SGM_PADW = 520;  // >= 63*8 + 7 + slack: window starts reach -(VPL*63+VPL-1)
+// VPL = 16 (D in 513..1024): a lane's window bytes start at -(16*63 + 12 + 3) = -1023 at the least and at W - 1 + 16*63 + 12 at the most; the
+// maps of such a call are laid out with this pad (sgm_padw), the bias of the window descriptor follows it.  VPL = 4 and 8 keep 520 and 1024.
+constexpr int SGM_PADW_WIDE = 1032;
+constexpr int sgm_padw_vpl(int vpl) { return vpl <= 8 ? SGM_PADW : SGM_PADW_WIDE; }
+constexpr int sgm_wbias_vpl(int vpl) { return vpl <= 8 ? 1024 : 2048; }   // >= the most negative window start (VPL*63 + VPL - 1 + 3)
+static inline int sgm_padw(int D) { return D <= 512 ? SGM_PADW : SGM_PADW_WIDE; }   // the host's: D <= 512 runs VPL 4 or 8, above that VPL 16
 
 struct SgmPassArgs {
 	const float *C[2];    // input cost volume(s), (H,W,ds)
@@ -38,6 +44,15 @@ struct SgmPassArgs {
 	float *ck[2];         // the recomputing vertical launches: volume v's checkpoint rows, (H / SGM_CK_ROWS, W, ds) -- L_down of the image rows
 	                      // y % SGM_CK_ROWS == SGM_CK_ROWS - 1, written by MODE 4 and read by sgm_updown_line (behind drop_h for the same reason)
 };
+
+// The two choices of a walk's form, stated once: the host asks them (launch_pass, sgm_sweeps_ck) and so does the device where a kernel holds
+// several forms (sgm_line_wide).  FAR: a volume of 2 GiB or more, 64-bit pixel addresses in every step.  Vector: 16-byte pieces -- the pixel
+// stride a multiple of 4 and every volume of the call 16-byte aligned (sgm_sweeps_ck fills both entries of each array; a null out2 is aligned).
+__host__ __device__ inline bool sgm_far(int H, int W, int ds) { return (int64_t)H * W * ds * 4 >= ((int64_t)1 << 31); }
+__host__ __device__ inline bool sgm_vec(const SgmPassArgs &A)
+{
+	return (A.ds & 3) == 0 && (((uintptr_t)A.C[0] | (uintptr_t)A.C[1] | (uintptr_t)A.out[0] | (uintptr_t)A.out[1] | (uintptr_t)A.out2[0] | (uintptr_t)A.out2[1]) & 15) == 0;
+}
 
 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
 
@@ -152,9 +167,9 @@ __device__ __forceinline__ void sgm_line(const SgmPassArgs &A, int wave)
 
 	const int dbase = VPL * lane;
 	const uint8_t *__restrict__ cls0 = A.cls0 + (int64_t)dirn * A.cls_plane;
-	// window bytes: buffer base = win row + x + SGM_PADW - WBIAS (wave-uniform), per-lane constant voffset
-	constexpr int WBIAS = 1024;  // >= the most negative window start (VPL*63 + VPL - 1 + 3)
-	const uint8_t *__restrict__ win = A.win + ((int64_t)((direction > 0 ? 0 : 1) * 4 + dirn) * H) * Wm + SGM_PADW - WBIAS;
+	// window bytes: buffer base = win row + x + PADW - WBIAS (wave-uniform), per-lane constant voffset
+	constexpr int WBIAS = sgm_wbias_vpl(VPL), PADW = sgm_padw_vpl(VPL);
+	const uint8_t *__restrict__ win = A.win + ((int64_t)((direction > 0 ? 0 : 1) * 4 + dirn) * H) * Wm + PADW - WBIAS;
 	// window start of chunk q at image column x: direction +1: x + VPL*lane + 4q ; -1: x - VPL*lane - 4q - 3
 	const int woff = (direction > 0 ? dbase : -dbase - 3) + WBIAS;
 	const int wq = direction > 0 ? 4 : -4;
@@ -638,10 +653,41 @@ __global__ void __launch_bounds__(256) sgm_updown_kernel(const SgmPassArgs A)
 
 constexpr int SGM_U_CK = 16;     // steps in flight of the checkpoint launch (MODE 4): a slot is a run of C and two class bytes
 
+// D in 513..1024: the line walk at VPL = 16.  Its forms are no kernels of their own: the library's kernel set is the one tests/kernel_inventory.txt
+// lists, so each lives inside the kernel that runs the same sweep at VPL = 8 on aligned volumes below 2 GiB with 8 steps in flight (below) -- an
+// instance that already takes more than 256 registers, i.e. one wave per SIMD (the fused horizontal one: under 256 with either walk), so that the
+// wider walk costs the D <= 512 path one uniform compare per wave and nothing else.  Which form runs is decided here as launch_pass decides it for
+// the narrower walks, by the same two functions (sgm_far, sgm_vec): FAR for a volume of 2 GiB, per element (MODE 1 only) without alignment.
+// Steps in flight: a step is 18 + 16 * NACC registers (StepData<16, NACC>); sized so that no form has scratch and none lifts its host kernel
+// out of its register class.  Not tuned.
+constexpr int SGM_U_WIDE = 4, SGM_U_WIDE_ELEM = 2;
+
+template <int DIRN, int MODE, bool ARGMIN, bool DUAL>
+__device__ __forceinline__ void sgm_line_wide(const SgmPassArgs &A, int wave)
+{
+	const bool far = sgm_far(A.H, A.W, A.ds);
+	if constexpr (MODE == 1) {   // mc_sgm2, the caller's volumes; the fused modes run on aligned volumes only (sgm_sweeps_ck requires it)
+		if (!sgm_vec(A)) {
+			if (far) sgm_line<DIRN, 16, MODE, ARGMIN, false, SGM_U_WIDE_ELEM, DUAL, true, false>(A, wave);
+			else sgm_line<DIRN, 16, MODE, ARGMIN, false, SGM_U_WIDE_ELEM, DUAL, false, false>(A, wave);
+			return;
+		}
+	}
+	// (no trimmed form of the horizontal launch at 16: it runs without the promise, which gives the same bits by sgm_sweeps' contract)
+	if (far) sgm_line<DIRN, 16, MODE, ARGMIN, true, SGM_U_WIDE, DUAL, true, false>(A, wave);
+	else sgm_line<DIRN, 16, MODE, ARGMIN, true, SGM_U_WIDE, DUAL, false, false>(A, wave);
+}
+
 template <int DIRN, int VPL, int MODE, bool ARGMIN, bool VEC, int U, bool DUAL, bool FAR>
 __global__ void __launch_bounds__(256) sgm_pass_kernel(const SgmPassArgs A)
 {
 	const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+	if constexpr (VPL == 8 && VEC && U == 8 && !FAR && MODE != 4) {
+		if (A.D > 512) {
+			sgm_line_wide<DIRN, MODE, ARGMIN, DUAL>(A, wave);
+			return;
+		}
+	}
 	// the fused horizontal launch holds both forms of its line walk and takes the trimmed one under the caller's promise (one uniform branch
 	// per wave); without it, and in every other instance, the walk is the code it was
 	if constexpr (DIRN == 0 && DUAL && MODE == 0 && VEC && !FAR && !ARGMIN) {

@@ -277,28 +277,43 @@ def _host(t, dtype, what):
 
 
 def Normalize_backward_input(grad_output, input, norm, grad_input):
-    """adcensus.Normalize_backward_input(grad_output, input, norm, grad_input) -- adcensus.cu:1359-1377."""
+    """adcensus.Normalize_backward_input(grad_output, input, norm, grad_input) -- adcensus.cu:1359-1377.  The reference takes every size
+    from `input` and reads the other three tensors at those sizes whatever theirs are; here a tensor of another size is refused."""
     _chk(grad_output, input, norm, grad_input)
+    if input.dim() != 4:
+        raise ValueError("Normalize_backward_input: input of size %s is not 4-D" % (tuple(input.shape),))
     N, C, H, W = input.shape
+    if grad_output.shape != input.shape or grad_input.shape != input.shape:
+        raise ValueError("Normalize_backward_input: input is %s, grad_output %s, grad_input %s" %
+                         (tuple(input.shape), tuple(grad_output.shape), tuple(grad_input.shape)))
+    if norm.numel() != N * H * W:
+        raise ValueError("Normalize_backward_input: norm holds %d elements, the input's %s need %d" % (norm.numel(), tuple(input.shape), N * H * W))
     _ops.check(_ops.load().mc_normalize_backward_input(_p(grad_output), _p(input), _p(norm), _p(grad_input), N, C, H, W, _stream()),
                "Normalize_backward_input")
 
 
 def Margin2(input, tmp, gradInput, margin, pow):
-    """adcensus.Margin2(input, tmp, gradInput, margin, pow) -- adcensus.cu:1425-1453 (the pair count is tmp's)."""
+    """adcensus.Margin2(input, tmp, gradInput, margin, pow) -- adcensus.cu:1425-1453 (the pair count is tmp's; an input or gradInput
+    that does not hold two elements per pair is refused, where the reference reads or writes past it)."""
     _chk(input, tmp, gradInput)
+    if input.numel() != 2 * tmp.numel() or gradInput.numel() != 2 * tmp.numel():
+        raise ValueError("Margin2: tmp holds %d pairs, input %d elements, gradInput %d" % (tmp.numel(), input.numel(), gradInput.numel()))
     _ops.check(_ops.load().mc_margin2(_p(input), _p(tmp), _p(gradInput), tmp.numel(), float(margin), int(pow), _stream()), "Margin2")
 
 
 def remove_nonvisible(y):
     """adcensus.remove_nonvisible(y) -- adcensus.cu:1734-1745, in place (rows of y:size(4))."""
     _chk(y)
+    if y.dim() < 1:
+        raise ValueError("remove_nonvisible: a map of size %s has no rows" % (tuple(y.shape),))
     _ops.check(_ops.load().mc_remove_nonvisible(_p(y), y.numel(), y.shape[-1], _stream()), "remove_nonvisible")
 
 
 def remove_occluded(y):
     """adcensus.remove_occluded(y) -- adcensus.cu:1761-1772, in place; every pixel is tested against the row as it was."""
     _chk(y)
+    if y.dim() < 1:
+        raise ValueError("remove_occluded: a map of size %s has no rows" % (tuple(y.shape),))
     _ops.check(_ops.load().mc_remove_occluded(_p(y), y.numel(), y.shape[-1], _stream()), "remove_occluded")
 
 

@@ -258,6 +258,25 @@ int mc_predict(const mc_params *p, const float *x0, const float *x1,
                float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out,
                float *disp_out, void *stream);
 
+/* mc_predict with three more optional (H,W) outputs, what the pipeline knows about every pixel of disp_out and otherwise drops; with all
+ * three NULL it IS mc_predict: the same launches, the same bits.
+ *   outlier_out  what outlier_detection(dispL0, dispR0, D) writes (adcensus.cu:878-899): 0 match, 1 occlusion, 2 mismatch -- the classes the
+ *                two interpolation stages fill in.  Written whenever both arg-min maps exist, whatever sm_skip / sm_terminate say.  With
+ *                lr_check = 0 the check runs for this map alone and disp_out is what it is without it; asking for it counts as a right-side
+ *                output (left_only is ignored).
+ *   cost_out     c(d): the final left volume at the disparity d that the sub-pixel stage reads (after the mismatch interpolation with
+ *                lr_check = 1, the arg-min otherwise); a NaN cost is written as read.
+ *   curv_out     2 * (cp + cn - 2 * cz), the stage's own denominator from the costs at d+1, d-1, d; 0 where d < 1 or d >= D-1.
+ * MC_EINVAL, before anything is launched or written: cost_out / curv_out where sm_skip / sm_terminate leave the sub-pixel stage out; one of
+ * the three overlapping disp_out, another output or the workspace. */
+int mc_predict_ex(const mc_params *p, const float *x0, const float *x1,
+                  const float *featL, const float *featR, int C,
+                  const float *rawL, const float *rawR, int D, int H, int W,
+                  void *workspace, size_t workspace_bytes,
+                  float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out,
+                  float *outlier_out, float *cost_out, float *curv_out,
+                  float *disp_out, void *stream);
+
 /* Timing hook for bench.py: the same pipeline with HIP events recorded on `stream`
  * at the stage boundaries of this call.  stage_ms[MC_N_STAGES] receives the summed
  * duration (ms) of each stage; the call synchronises the stream to read them. */

@@ -409,9 +409,20 @@ int mc_predict(const mc_params *p, const float *x0, const float *x1, const float
                const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
                float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out, float *disp_out, void *stream)
 {
+	return mc_predict_ex(p, x0, x1, featL, featR, C, rawL, rawR, D, H, W, workspace, workspace_bytes, volL_out, volR_out, dispL0_out, dispR0_out,
+	                     nullptr, nullptr, nullptr, disp_out, stream);
+}
+
+int mc_predict_ex(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,
+                  const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
+                  float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out, float *outlier_out, float *cost_out, float *curv_out,
+                  float *disp_out, void *stream)
+{
 	StageTimer tm;
+	PredictExtras ex;
+	ex.outlier = outlier_out; ex.cost = cost_out; ex.curv = curv_out;
 	return predict_impl(p, x0, x1, featL, featR, C, rawL, rawR, D, H, W, workspace, workspace_bytes, volL_out, volR_out,
-	                    dispL0_out, dispR0_out, disp_out, as_stream(stream), tm);
+	                    dispL0_out, dispR0_out, disp_out, as_stream(stream), tm, ex);
 }
 
 int mc_predict_timed(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,

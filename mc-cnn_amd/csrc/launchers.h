@@ -21,6 +21,11 @@ constexpr int MC_MIS_MASK_MAX_PIXELS = 524288;   // a 64 KiB mask
 int interpolate_occlusion(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st, unsigned *mask = nullptr);
 int interpolate_mismatch(const float *d0, const float *outlier, float *out, int H, int W, hipStream_t st, const unsigned *mask = nullptr);
 int subpixel(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st);
+// subpixel with the stage's two confidence maps, (H,W) each, either may be null: cost_out = c(d), curv_out = 2 (cp + cn - 2 cz), 0 where d has no
+// two neighbours.  subpixel is this with both null: the same kernel, which then loads and stores nothing more.  (A name of its own, no default
+// arguments on subpixel: the host checks of predict.hip define subpixel as it stands above.)
+int subpixel_conf(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st, float *cost_out,
+                  float *curv_out);
 int median2d(const float *img, float *out, int H, int W, int k, hipStream_t st);
 int mean2d(const float *img, const float *kernel, float *out, int H, int W, int ks, float alpha2, hipStream_t st);
 int normalize_forward(const float *in, float *norm, float *out, int N, int C, int H, int W, hipStream_t st);
@@ -128,9 +133,12 @@ struct StageTimer {   // mc_predict_timed: an event at every stage boundary
 	void mark(int stage);
 	void collect(float out[MC_N_STAGES]);
 };
+// mc_predict_ex's optional (H,W) maps: the LR check's classes (0 match, 1 occlusion, 2 mismatch), and the sub-pixel stage's cost at the
+// disparity it reads and the curvature of the cost curve there
+struct PredictExtras { float *outlier = nullptr, *cost = nullptr, *curv = nullptr; };
 int predict_impl(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,
                  const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
                  float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out, float *disp_out, hipStream_t st,
-                 StageTimer &tm);
+                 StageTimer &tm, const PredictExtras &ex = PredictExtras());
 
 }  // namespace mc

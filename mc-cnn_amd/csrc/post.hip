@@ -589,8 +589,12 @@ int interpolate_mismatch(const float *d0, const float *outlier, float *out, int 
 
 // ---- subpixel_enchancement, adcensus.cu:1205-1220 ----------------------------------------------
 // cost of (pixel p, disparity d) is vol[d*sd + p*sp]: (D,H,W): sd=HW, sp=1 ; (H,W,ds): sd=1, sp=ds.
+// cost_out / curv_out (mc_predict_ex, either may be null): the two confidence measures the stage has in its hands, c(d) and the
+// curvature 2 (cp + cn - 2 cz) of the cost curve at d -- `denom` itself; 0 where the stage reads no neighbours.  Both null: the
+// kernel loads and stores what it always did.  Only cost_out adds a load, of c(d) at d = 0 and d = disp_max - 1.
 __global__ void __launch_bounds__(256) subpixel_kernel(const float *__restrict__ d0, const float *__restrict__ c2,
-                                                       float *__restrict__ out, int64_t size, int64_t sd, int64_t sp, int disp_max)
+                                                       float *__restrict__ out, int64_t size, int64_t sd, int64_t sp, int disp_max,
+                                                       float *__restrict__ cost_out, float *__restrict__ curv_out)
 {
 	const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (id >= size) return;
@@ -604,15 +608,27 @@ __global__ void __launch_bounds__(256) subpixel_kernel(const float *__restrict__
 		if ((double)denom > 1e-5) {
 			res = (float)((double)d - fmin(1.0, fmax(-1.0, (double)((cp - cn) / denom))));
 		}
+		if (cost_out) cost_out[id] = cz;
+		if (curv_out) curv_out[id] = denom;
+	} else {
+		// (a disparity outside [0, disp_max) is none of the pipeline's: no cost to read)
+		if (cost_out) cost_out[id] = (0 <= d && d < disp_max) ? c2[d * sd + id * sp] : __int_as_float(0x7fc00000);
+		if (curv_out) curv_out[id] = 0;
 	}
 	out[id] = res;
 }
 
-int subpixel(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st)
+int subpixel_conf(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st, float *cost_out,
+                  float *curv_out)
 {
 	const int64_t size = (int64_t)H * W;
-	hipLaunchKernelGGL(subpixel_kernel, dim3(cdiv(size, 256)), dim3(256), 0, st, d0, vol, out, size, sd, sp, D);
+	hipLaunchKernelGGL(subpixel_kernel, dim3(cdiv(size, 256)), dim3(256), 0, st, d0, vol, out, size, sd, sp, D, cost_out, curv_out);
 	return check_launch("subpixel_enchancement");
+}
+
+int subpixel(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st)
+{
+	return subpixel_conf(d0, vol, out, D, H, W, sd, sp, st, nullptr, nullptr);
 }
 
 // ---- median2d, adcensus.cu:1575-1594 ------------------------------------------------------------

@@ -13,6 +13,10 @@ namespace mc {
 // sgm_maps_bytes / sgm_prep alone.  Without them a range above 512 is refused (predict_impl), never run on the narrower maps.
 size_t sgm_maps_bytes_d(int H, int W, int D) __attribute__((weak));
 int sgm_prep_d(const float *x0, const float *x1, void *maps, int H, int W, int D, float tau_so, hipStream_t st) __attribute__((weak));
+// The sub-pixel stage with its confidence maps (post.hip), weak HERE only for the same reason: those host checks define subpixel alone, and
+// no call of theirs asks for a map.  Without it such a call is refused (predict_impl).
+int subpixel_conf(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st, float *cost_out,
+                  float *curv_out) __attribute__((weak));
 
 // gaussian(sigma), main.lua:528-540, double on the host.  mc_predict reads it from DEVICE memory, cached per (device, sigma): allocated and
 // uploaded synchronously at first use (complete before any stream can be given it) and never freed; it depends on the preset alone.
@@ -146,8 +150,9 @@ struct LaneJoin {
 };
 
 // -sm_terminate / -sm_skip (main.lua:956,988-1040) are identical for both directions, so for the three volume stages they
-// reduce to effective iteration counts
-struct StageCounts { int cbca1, sgm, cbca2; bool active_after; };
+// reduce to effective iteration counts; for the stages on the left disparity behind them (main.lua:1054-1079), to whether each runs.
+// The one place that reads sm_terminate / sm_skip: predict_impl runs what it says, and refuses a map of a stage that it leaves out.
+struct StageCounts { int cbca1, sgm, cbca2; bool occlusion, mismatch, subpixel, median, bilateral; };
 static StageCounts stage_counts(const mc_params *p)
 {
 	StageCounts c;
@@ -158,7 +163,20 @@ static StageCounts stage_counts(const mc_params *p)
 	sm_active = sm_active && p->sm_terminate != MC_SM_SGM;
 	c.cbca2 = (sm_active && p->sm_skip != MC_SKIP_CBCA) ? p->cbca_i2 : 0;
 	sm_active = sm_active && p->sm_terminate != MC_SM_CBCA2;
-	c.active_after = sm_active;
+	// a stage runs if the method is still active and the stage is not skipped; then -sm_terminate applies
+	auto stage = [&](int skip, int terminate) {
+		const bool runs = sm_active && p->sm_skip != skip;
+		sm_active = sm_active && p->sm_terminate != terminate;
+		return runs;
+	};
+	c.occlusion = c.mismatch = false;
+	if (p->lr_check) {   // (without the LR check the two stages do not exist: their -sm_terminate names end nothing)
+		c.occlusion = stage(MC_SKIP_OCCLUSION, MC_SM_OCCLUSION);
+		c.mismatch = stage(MC_SKIP_OCCLUSION, MC_SM_MISMATCH);
+	}
+	c.subpixel = stage(MC_SKIP_SUBPIXEL, MC_SM_SUBPIXEL);
+	c.median = stage(MC_SKIP_MEDIAN, MC_SM_MEDIAN);
+	c.bilateral = stage(MC_SKIP_BILATERAL, MC_SM_BILATERAL);
 	return c;
 }
 
@@ -226,7 +244,7 @@ void StageTimer::collect(float out[MC_N_STAGES])
 int predict_impl(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,
                  const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
                  float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out, float *disp_out, hipStream_t st,
-                 StageTimer &tm)
+                 StageTimer &tm, const PredictExtras &ex)
 {
 	MC_REQUIRE(p && x0 && x1 && disp_out && workspace, "mc_predict: null argument");
 	MC_REQUIRE(dims_ok(D, H, W), "mc_predict: bad dims D=%d H=%d W=%d", D, H, W);
@@ -244,6 +262,26 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	const Plan pl = make_plan(p, D, H, W, workspace);   // (addresses only: nothing is touched before the two checks)
 	MC_REQUIRE(workspace_bytes >= pl.total, "mc_predict: workspace %zu < %zu bytes", workspace_bytes, pl.total);
 	MC_REQUIRE((uintptr_t)workspace % 256 == 0, "mc_predict: workspace must be 256-byte aligned");
+	const StageCounts sc = stage_counts(p);   // -sm_terminate / -sm_skip as effective iteration counts and stages that run
+	{   // mc_predict_ex's maps: none of a stage that does not run, none on top of anything else the call reads back or works in
+		const size_t map_bytes = (size_t)H * W * sizeof(float), vol_bytes = (size_t)D * map_bytes;
+		struct Range { const char *name; const void *at; size_t bytes; };
+		const Range extras[3] = {{"outlier_out", ex.outlier, map_bytes}, {"cost_out", ex.cost, map_bytes}, {"curv_out", ex.curv, map_bytes}};
+		const Range others[6] = {{"disp_out", disp_out, map_bytes}, {"volL_out", volL_out, vol_bytes}, {"volR_out", volR_out, vol_bytes},
+		                         {"dispL0_out", dispL0_out, map_bytes}, {"dispR0_out", dispR0_out, map_bytes}, {"the workspace", workspace, workspace_bytes}};
+		auto overlap = [](const Range &a, const Range &b) {
+			return a.at && b.at && (uintptr_t)a.at < (uintptr_t)b.at + b.bytes && (uintptr_t)b.at < (uintptr_t)a.at + a.bytes;
+		};
+		for (int i = 0; i < 3; ++i) {
+			if (i > 0 && extras[i].at) {
+				MC_REQUIRE(sc.subpixel, "mc_predict_ex: %s is written by the sub-pixel stage, which sm_terminate=%d / sm_skip=%d leave out",
+				           extras[i].name, p->sm_terminate, p->sm_skip);
+				MC_REQUIRE(subpixel_conf, "mc_predict_ex: %s needs the sub-pixel stage's maps, which this program does not link", extras[i].name);
+			}
+			for (const Range &o : others) MC_REQUIRE(!overlap(extras[i], o), "mc_predict_ex: %s overlaps %s", extras[i].name, o.name);
+			for (int j = 0; j < i; ++j) MC_REQUIRE(!overlap(extras[i], extras[j]), "mc_predict_ex: %s overlaps %s", extras[i].name, extras[j].name);
+		}
+	}
 
 	const bool have_ck = workspace_bytes >= pl.total_ck && sgm_sweeps_ck != nullptr;   // the workspace holds the SGM's checkpoint slots
 
@@ -256,9 +294,7 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 
 	// index 0 = left volume (direction -1), 1 = right volume (direction +1)  (main.lua:986)
 	const int direction[2] = {-1, 1};
-	const StageCounts sc = stage_counts(p);   // -sm_terminate / -sm_skip as effective iteration counts
 	const int n_cbca1 = sc.cbca1, n_sgm = sc.sgm, n_cbca2 = sc.cbca2;
-	bool sm_active = sc.active_after;
 	const bool use_cbca = (n_cbca1 + n_cbca2) > 0;
 	tm.mark(-1);
 
@@ -279,8 +315,8 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	auto other = [&](int v) -> float * { return cur[v] == pl.bufA[v] ? pl.bufB[v] : pl.bufA[v]; };
 	bool hwd;  // layout of cur[]
 	// direction +1 (the right volume) is skipped where the reference skips it: dataset mb outside `-a predict`
-	// (mb_directions, main.lua:953-955) -- only when nothing of it is asked for
-	const int nvol = (p->left_only && !p->lr_check && !volR_out && !dispR0_out) ? 1 : 2;
+	// (mb_directions, main.lua:953-955) -- only when nothing of it is asked for (the class map compares the two arg-min maps)
+	const int nvol = (p->left_only && !p->lr_check && !volR_out && !dispR0_out && !ex.outlier) ? 1 : 2;
 	// n CBCA iterations on the (D,H,W) volumes, ping-pong between the two buffers of each side (instead of vol:copy(tmp)).
 	// Where the pair's route may be the texture one (cfg.lean), the iterations go in PAIRS: cbca_lean2x runs two passes in one launch
 	// (cur -> dst) out of a list written once per pair and direction; the kernels of the other routes -- which one runs is decided on
@@ -467,7 +503,7 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	// ---- (C) post-processing on the LEFT disparity, main.lua:1054-1081 ----
 	// every stage reads `d` and writes the next free image; -sm_skip / -sm_terminate drop stages (main.lua:1057-1079)
 	float *d = dispv[0];
-	float *outl = pl.img[4];
+	float *outl = ex.outlier ? ex.outlier : pl.img[4];   // the LR check's classes: in the caller's map where one is given, and read from there
 	int nfree = 0;
 	float *freeimg[3] = {pl.img[2], pl.img[3], pl.img[5]};
 	auto next = [&]() -> float * {
@@ -476,14 +512,13 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 		++nfree;
 		return r;
 	};
-	// one stage: if it is active and not skipped it runs into the next free image, which becomes `d`; then -sm_terminate applies
-	auto stage = [&](int skip, int terminate, auto &&run) -> int {
-		if (sm_active && p->sm_skip != skip) {
+	// one stage: if it runs (stage_counts) it runs into the next free image, which becomes `d`
+	auto stage = [&](bool runs, auto &&run) -> int {
+		if (runs) {
 			float *o = next();
 			if (const int rc1 = run(o)) return rc1;
 			d = o;
 		}
-		sm_active = sm_active && p->sm_terminate != terminate;
 		return 0;
 	};
 	if (p->lr_check) {
@@ -491,19 +526,22 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 		// the occlusion stage leaves the mismatch marks as a bitmask for the ray walk, in the cross arms' area (dead since the last
 		// aggregation pass); where that stage does not run there is none and the walk reads the marks themselves
 		const unsigned *mis_mask = nullptr;
-		RUN(stage(MC_SKIP_OCCLUSION, MC_SM_OCCLUSION, [&](float *o) {
+		RUN(stage(sc.occlusion, [&](float *o) {
 			unsigned *m = HW <= MC_MIS_MASK_MAX_PIXELS ? (unsigned *)pl.x0c : nullptr;
 			mis_mask = m;
 			return interpolate_occlusion(d, outl, o, H, W, st, m);
 		}));
-		RUN(stage(MC_SKIP_OCCLUSION, MC_SM_MISMATCH, [&](float *o) { return interpolate_mismatch(d, outl, o, H, W, st, mis_mask); }));
+		RUN(stage(sc.mismatch, [&](float *o) { return interpolate_mismatch(d, outl, o, H, W, st, mis_mask); }));
+	} else if (ex.outlier) {
+		RUN(outlier_detection(d, dispv[1], ex.outlier, H, W, D, st));   // the classes alone: nothing here reads them
 	}
 	// subpixel on the LEFT volume (vol of the last loop iteration, main.lua:1068)
-	RUN(stage(MC_SKIP_SUBPIXEL, MC_SM_SUBPIXEL, [&](float *o) {
-		return hwd ? subpixel(d, cur[0], o, D, H, W, 1, ds, st) : subpixel(d, cur[0], o, D, H, W, HW, 1, st);
+	RUN(stage(sc.subpixel, [&](float *o) {
+		const int64_t sd = hwd ? 1 : HW, sp = hwd ? ds : 1;
+		return (ex.cost || ex.curv) ? subpixel_conf(d, cur[0], o, D, H, W, sd, sp, st, ex.cost, ex.curv) : subpixel(d, cur[0], o, D, H, W, sd, sp, st);
 	}));
-	RUN(stage(MC_SKIP_MEDIAN, MC_SM_MEDIAN, [&](float *o) { return median2d(d, o, H, W, p->median_k, st); }));
-	if (sm_active && p->sm_skip != MC_SKIP_BILATERAL) {
+	RUN(stage(sc.median, [&](float *o) { return median2d(d, o, H, W, p->median_k, st); }));
+	if (sc.bilateral) {
 		const float *gk = nullptr;
 		RUN(gaussian_cached(p->blur_sigma, gk));
 		RUN(mean2d(d, gk, disp_out, H, W, gaussian_ks(p->blur_sigma), p->blur_t, st));

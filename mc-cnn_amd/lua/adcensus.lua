@@ -81,6 +81,13 @@ int mc_predict(const mc_params *p, const float *x0, const float *x1,
                void *workspace, size_t workspace_bytes,
                float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out,
                float *disp_out, void *stream);
+int mc_predict_ex(const mc_params *p, const float *x0, const float *x1,
+                  const float *featL, const float *featR, int C,
+                  const float *rawL, const float *rawR, int D, int H, int W,
+                  void *workspace, size_t workspace_bytes,
+                  float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out,
+                  float *outlier_out, float *cost_out, float *curv_out,
+                  float *disp_out, void *stream);
 int mc_read_png16(const char *fname, float *img, int64_t capacity, int *height, int *width);
 int mc_write_png16(const float *img, int height, int width, const char *fname);
 int mc_write_pfm(const float *img, int height, int width, const char *fname);
@@ -284,12 +291,17 @@ end
 --            (adcensus.ad / census / fc_stack output, NaN outside the valid range)
 --   border_n (get_window_size(net_te) - 1) / 2 for arch fast (fix_border, main.lua:922-927); ignored otherwise
 --   both     true for `-a predict` (both directions; returns the left.bin / right.bin volumes), false otherwise
+--   extras   optional table {outlier=, cost=, curvature=} of CudaTensors, any subset: each is resized to (1,1,H,W) and filled by
+--            mc_predict_ex -- the LR check's classes (0 match, 1 occlusion, 2 mismatch; on 'mb' the check runs for this map alone),
+--            the final left volume at the disparity the sub-pixel stage reads, and the curvature 2 (c[d+1] + c[d-1] - 2 c[d]) of the
+--            cost curve there (0 at d = 0 and d = disp_max - 1).  cost / curvature with -sm_skip subpixel_enchancement, or a
+--            -sm_terminate in front of that stage, is an error.  Without the table the call is mc_predict.
 -- Returns disp (1,1,H,W) and, when `both`, volL, volR (1,disp_max,H,W).
 local SM_TERMINATE = {[''] = 0, cnn = 1, cbca1 = 2, sgm = 3, cbca2 = 4, occlusion = 5, mismatch = 6,
                       subpixel_enchancement = 7, median = 8, bilateral = 9}
 local SM_SKIP = {[''] = 0, cbca = 1, sgm = 2, occlusion = 3, subpixel_enchancement = 4, median = 5, bilateral = 6}
 local predict_ws = torch.CudaTensor()
-function adcensus.predict(o, dataset, arch, x_batch, input, disp_max, border_n, both)
+function adcensus.predict(o, dataset, arch, x_batch, input, disp_max, border_n, both, extras)
    local p = ffi.new('mc_params')
    p.L1, p.tau1, p.cbca_i1, p.cbca_i2 = o.L1, o.tau1, o.cbca_i1, o.cbca_i2
    p.pi1, p.pi2, p.sgm_i, p.sgm_q1, p.sgm_q2 = o.pi1, o.pi2, o.sgm_i, o.sgm_q1, o.sgm_q2
@@ -318,7 +330,25 @@ function adcensus.predict(o, dataset, arch, x_batch, input, disp_max, border_n, 
    ptr(x_batch, 'predict'); ptr(input, 'predict')
    local fl, fr, rl, rr = nil, nil, nil, nil
    if arch == 'fast' then fl, fr = input[1]:data(), input[2]:data() else rl, rr = input[1]:data(), input[2]:data() end
-   check(lib.mc_predict(p, x0, x1, fl, fr, C, rl, rr, disp_max, H, W, ws, need, pl, pr, nil, nil, disp:data(), nil), 'predict')
+   if extras == nil then
+      check(lib.mc_predict(p, x0, x1, fl, fr, C, rl, rr, disp_max, H, W, ws, need, pl, pr, nil, nil, disp:data(), nil), 'predict')
+      return disp, volL, volR
+   end
+   local ex = {}
+   for _, k in ipairs({'outlier', 'cost', 'curvature'}) do
+      local t = extras[k]
+      if t ~= nil then
+         if torch.typename(t) ~= 'torch.CudaTensor' then
+            error(('predict: extras.%s: torch.CudaTensor expected, got %s'):format(k, torch.typename(t) or type(t)), 2)
+         end
+         ex[k] = t:resize(1, 1, H, W):data()
+      end
+   end
+   for k in pairs(extras) do
+      if k ~= 'outlier' and k ~= 'cost' and k ~= 'curvature' then error('predict: unknown extra ' .. tostring(k), 2) end
+   end
+   check(lib.mc_predict_ex(p, x0, x1, fl, fr, C, rl, rr, disp_max, H, W, ws, need, pl, pr, nil, nil, ex.outlier, ex.cost, ex.curvature,
+                           disp:data(), nil), 'predict')
    return disp, volL, volR
 end
 

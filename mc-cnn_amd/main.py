@@ -7,7 +7,9 @@ RGB to luma, normalises each to zero mean / unit (unbiased) std on the host, upl
 (arch fast: l1 x [3x3 conv, pad 1, ReLU] with no ReLU after the last conv, then Normalize2 -- main.lua:727-746; the
 convolutions are `mc_conv3x3`, a hand-written fp32-MFMA implicit GEMM of libmcadcensus.so, like everything after them), then the post-CNN
 pipeline in one `mc_predict` call, and writes `left.bin`, `right.bin` (1,D,H,W) and `disp.bin` (1,1,H,W), raw float32,
-with the reference's messages.  `-a time` is main.lua:1140-1167 (min of N runs on an uninitialised batch).
+with the reference's messages.  `-a time` is main.lua:1140-1167 (min of N runs on an uninitialised batch).  `-a predict -extras` also
+writes `outlier.bin`, `cost.bin` and `curvature.bin` (1,1,H,W) next to `disp.bin`: the LR check's class of every pixel (0 match, 1 occlusion,
+2 mismatch) and the two confidence measures of the sub-pixel stage (`mc_predict_ex`; no counterpart in main.lua).
 
 Architectures: fast, slow (feature net + `mc_fc_stack`, main.lua:958-983; `-fc_mode bf16x3` takes the FC stack's products as three
 bf16 products each, `mc_fc_split_stack` of libmcfcsplit.so, wherever arch slow predicts; the default `-fc_mode fp32` is `mc_fc_stack`;
@@ -97,6 +99,7 @@ def parse(argv):
     ap.add_argument("-right", default="")
     ap.add_argument("-disp_max", type=int, default=228 if dataset != "mb" else 200)
     ap.add_argument("-tiny", action="store_true")
+    ap.add_argument("-extras", action="store_true", help="-a predict: also write outlier.bin, cost.bin and curvature.bin (mc_predict_ex)")
     add_fc_mode_flag(ap)
     add_conv_mode_flag(ap)
     ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
@@ -117,6 +120,8 @@ def parse(argv):
                          "-a train_tr | train_all | test_te through train_mb_slow.parse; -a test_all on mb and -a submit are "
                          "out of scope)"
                          % (opt.a, dataset, arch, " | ".join(TRAIN_ACTIONS)))
+    if opt.extras and opt.a != "predict":
+        raise SystemExit("main.py: -extras writes outlier.bin, cost.bin and curvature.bin next to disp.bin and goes with -a predict only")
     if getattr(opt, "at", 0) == 1 and opt.data_dir:
         raise SystemExit("main.py: -at 1 reads data.kitti and data.kitti2015 together (main.lua:403-426) and takes no -data_dir")
     return dataset, arch, opt, pipeline_prm(t, opt)
@@ -284,7 +289,8 @@ def main(argv=None):
     prm["border_n"] = len(layers)  # (1 + l1*(3-1) - 1) / 2, main.lua:382-391,923
     conv_mode = getattr(opt, "conv_mode", "fp32")   # the feature net's convolutions wherever this command line predicts
 
-    def run(x_batch, D, workspace=None, want_volumes=False):
+    def run(x_batch, D, workspace=None, want_volumes=False, extras=False):
+        more = dict(want_outlier=True, want_confidence=True) if extras else {}   # -extras: mc_predict_ex's three maps
         if not learned:  # main.lua:932-942: hand-crafted costs straight from the image pair, no border fix
             from . import adcensus
             cost = adcensus.ad if arch == "ad" else adcensus.census
@@ -295,12 +301,12 @@ def main(argv=None):
             adcensus.fill_nan(volR)
             cost(x_batch[0:1], x_batch[1:2], volL, -1)
             cost(x_batch[1:2], x_batch[0:1], volR, 1)
-            return stereo_predict_fused(x_batch, prm, D, raw=(volL, volR), workspace=workspace, want_volumes=want_volumes)
+            return stereo_predict_fused(x_batch, prm, D, raw=(volL, volR), workspace=workspace, want_volumes=want_volumes, **more)
         if arch == "fast":
             return stereo_predict_fused(x_batch, prm, D, feat=features_fast(x_batch, layers, conv_mode), workspace=workspace,
-                                        want_volumes=want_volumes)
+                                        want_volumes=want_volumes, **more)
         raw = raw_volumes_slow(features_slow(x_batch, layers, conv_mode), fc_layers, D, prm["border_n"], fc_mode=getattr(opt, "fc_mode", "fp32"))
-        return stereo_predict_fused(x_batch, prm, D, raw=raw, workspace=workspace, want_volumes=want_volumes)
+        return stereo_predict_fused(x_batch, prm, D, raw=raw, workspace=workspace, want_volumes=want_volumes, **more)
     if opt.a in TRAIN_ACTIONS:
         if mod is None:
             from . import train as mod
@@ -339,7 +345,7 @@ def main(argv=None):
         x0, x1 = rgb2y(x0), rgb2y(x1)
     D = opt.disp_max
     x_batch = torch.from_numpy(np.stack([normalize(x0), normalize(x1)])).to(dev)  # (2,1,H,W)
-    res = run(x_batch, D, want_volumes=True)
+    res = run(x_batch, D, want_volumes=True, extras=opt.extras)
     torch.cuda.synchronize()
     H, W = x_batch.shape[2:]
     for name, key in (("right", "volR"), ("left", "volL")):  # main.lua:954-955 writes right.bin first
@@ -347,6 +353,10 @@ def main(argv=None):
         write_bin("%s.bin" % name, res[key].cpu().numpy())
     print("Writing disp.bin, %d x %d x %d x %d" % (1, 1, H, W))
     write_bin("disp.bin", res["disp"].cpu().numpy())
+    if opt.extras:
+        for name, key in (("outlier", "outlier"), ("cost", "cost"), ("curvature", "curvature")):
+            print("Writing %s.bin, %d x %d x %d x %d" % (name, 1, 1, H, W))
+            write_bin("%s.bin" % name, res[key].cpu().numpy())
     return 0
 
 

@@ -36,8 +36,11 @@ def stereo_predict(x_batch, params, disp_max, feat=None, raw=None, return_all=Fa
     """Op-by-op mirror of stereo_predict(x_batch, id), main.lua:929-1082.
 
     x_batch: (2,1,H,W) normalised images.  Returns disp[2] (1,1,H,W); with
-    return_all also the final volumes (what left.bin / right.bin hold) and the
-    intermediate maps."""
+    return_all also the final volumes (what left.bin / right.bin hold), the
+    intermediate maps and the three per-pixel maps of mc_predict_ex: `outlier`
+    (the LR check's classes; without the LR check it runs for the map alone),
+    `cost` and `curvature` (the left volume around the disparity the sub-pixel
+    stage reads), each (1,1,H,W)."""
     p = make_params(params)
     x0, x1, H, W = _img2(x_batch)
     D = int(disp_max)
@@ -90,12 +93,30 @@ def stereo_predict(x_batch, params, disp_max, feat=None, raw=None, return_all=Fa
         adcensus.outlier_detection(d, disp[1], outlier, D)
         d = adcensus.interpolate_occlusion(d, outlier)
         d = adcensus.interpolate_mismatch(d, outlier)
+    elif return_all:
+        adcensus.outlier_detection(d, disp[1], outlier, D)
+    if return_all:
+        cost, curvature = confidence_maps(d, out_vols[-1])
     d = adcensus.subpixel_enchancement(d, out_vols[-1], D)  # vol = LEFT volume, main.lua:1068
     d = adcensus.median2d(d, p.median_k)
     d = adcensus.mean2d(d, adcensus.gaussian(p.blur_sigma).to(dev), p.blur_t)
     if return_all:
-        return dict(disp=d, volL=out_vols[-1], volR=out_vols[1], dispL0=disp[2], dispR0=disp[1], outlier=outlier)
+        return dict(disp=d, volL=out_vols[-1], volR=out_vols[1], dispL0=disp[2], dispR0=disp[1], outlier=outlier, cost=cost,
+                    curvature=curvature)
     return d
+
+
+def confidence_maps(d, vol):
+    """mc_predict_ex's cost_out and curv_out with torch indexing: for the integer disparity map d (1,1,H,W) and the volume
+    (1,D,H,W), c(d) and 2 * (c(d+1) + c(d-1) - 2 * c(d)) in float32 in that order, the curvature 0 where d < 1 or d >= D - 1."""
+    D = vol.shape[1]
+    di = d.to(torch.int64)
+    cz = vol.gather(1, di)
+    cn = vol.gather(1, (di - 1).clamp(0, D - 1))
+    cp = vol.gather(1, (di + 1).clamp(0, D - 1))
+    curvature = 2 * ((cp + cn) - 2 * cz)
+    inner = (di >= 1) & (di < D - 1)
+    return cz, torch.where(inner, curvature, torch.zeros_like(curvature))
 
 
 def workspace_bytes(params, disp_max, H, W, C_feat=0, full=False):
@@ -121,8 +142,12 @@ class Workspace:
 
 
 def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspace=None, want_volumes=False,
-                         want_disp0=False, out=None, timed=False):
-    """The whole of stereo_predict from the cost-volume stage on, in one C-ABI call."""
+                         want_disp0=False, out=None, timed=False, want_outlier=False, want_confidence=False):
+    """The whole of stereo_predict from the cost-volume stage on, in one C-ABI call.
+
+    want_outlier adds res["outlier"], the LR check's class per pixel (0 match, 1 occlusion, 2 mismatch); want_confidence adds
+    res["cost"] and res["curvature"], the final left volume at the disparity the sub-pixel stage reads and the curvature of the cost
+    curve there.  Each is (1,1,H,W); with either flag the call is mc_predict_ex, otherwise mc_predict."""
     p = make_params(params)
     x0, x1, H, W = _img2(x_batch)
     D = int(disp_max)
@@ -159,7 +184,15 @@ def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspa
         res["dispL0"] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
         res["dispR0"] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
         dl, dr = res["dispL0"].data_ptr(), res["dispR0"].data_ptr()
-    check(lib.mc_predict(C.byref(p), x0.data_ptr(), x1.data_ptr(), fl, fr, Cn, rl, rr, D, H, W, workspace.ptr,
-                         ws_bytes, vl, vr, dl, dr, out.data_ptr(), st), "mc_predict")
+    if want_outlier or want_confidence:
+        names = (("outlier",) if want_outlier else ()) + (("cost", "curvature") if want_confidence else ())
+        for name in names:
+            res[name] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
+        ex = [res[name].data_ptr() if name in res else None for name in ("outlier", "cost", "curvature")]
+        check(lib.mc_predict_ex(C.byref(p), x0.data_ptr(), x1.data_ptr(), fl, fr, Cn, rl, rr, D, H, W, workspace.ptr,
+                                ws_bytes, vl, vr, dl, dr, ex[0], ex[1], ex[2], out.data_ptr(), st), "mc_predict_ex")
+    else:
+        check(lib.mc_predict(C.byref(p), x0.data_ptr(), x1.data_ptr(), fl, fr, Cn, rl, rr, D, H, W, workspace.ptr,
+                             ws_bytes, vl, vr, dl, dr, out.data_ptr(), st), "mc_predict")
     del keep
     return res

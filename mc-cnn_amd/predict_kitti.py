@@ -14,6 +14,11 @@ thread while the GPU runs the current ones, and the pairs alternate between K sl
 pair's upload / feature net / mc_predict / download overlap its neighbours' (bench.py's `pipelined` record: 2.63 -> 2.3-2.5 ms per pair
 on the GPU side at KITTI size).  Results do not depend on K.
 
+`-sparse` (no counterpart in the reference) keeps only the pixels that passed the left-right check, class 0 of `mc_predict_ex`'s outlier
+map, i.e. those that were measured and not filled in by the two interpolation stages: `submit -sparse` writes 0, KITTI's "no estimate",
+everywhere else; `test -sparse` prints `i err density` per pair -- the 3-pixel error over the ground-truth pixels of class 0 and their
+share of all ground-truth pixels -- and then the two means.
+
 Same file layout as the reference: <path>/{training,testing}/image_{0,1}/%06d_10.png, ground truth
 <path>/training/disp_noc/%06d_10.png (PNG16, value/256, 0 = no ground truth), output out/%06d_10.png.
 """
@@ -41,12 +46,24 @@ def three_pixel_error(disp, ground_truth):
     return float(bad.sum()) / float(mask.sum())
 
 
-def run(action, path, predict_pair, world=1, rank=0, out_dir="out", n_pairs=None, log=print, in_flight=1):
+def sparse_error(disp, ground_truth, outlier):
+    """-sparse: (3-pixel error over the ground-truth pixels of outlier class 0, their share of all ground-truth pixels); an error of 0
+    where there is no such pixel."""
+    mask = ground_truth != 0
+    kept = mask & (outlier == 0)
+    bad = (np.abs(disp - ground_truth) > 3) & kept
+    n_kept, n_gt = float(kept.sum()), float(mask.sum())
+    return (float(bad.sum()) / n_kept if n_kept else 0.0), (n_kept / n_gt if n_gt else 0.0)
+
+
+def run(action, path, predict_pair, world=1, rank=0, out_dir="out", n_pairs=None, log=print, in_flight=1, sparse=False):
     """predict_pair(left_png, right_png) -> (H,W) float32 disparity.  Returns (error sum, pairs done) of this rank.
+    sparse: predict_pair gives (disparity, outlier classes), both (H,W); `submit` writes 0 where the class is not 0, `test` scores the
+    pixels of class 0 alone, logs (i, err, density) and returns (error sum, pairs done, density sum).
     A predict_pair object with .submit(left_png, right_png) -> ticket and .result(ticket) -> disparity is driven with up to
     `in_flight` pairs submitted ahead of the one whose result is being scored / written (same order, same results)."""
     n = N_PAIRS[action] if n_pairs is None else n_pairs
-    err_sum, done = 0.0, 0
+    err_sum, done, density_sum = 0.0, 0, 0.0
     todo = list(shard(n, world, rank))
     staged = hasattr(predict_pair, "submit") and in_flight > 1
     tickets = {}
@@ -56,21 +73,32 @@ def run(action, path, predict_pair, world=1, rank=0, out_dir="out", n_pairs=None
             while ahead < len(todo) and ahead < k + in_flight:
                 tickets[todo[ahead]] = predict_pair.submit(*pair_paths(path, action, todo[ahead]))
                 ahead += 1
-            disp = np.asarray(predict_pair.result(tickets.pop(i)), np.float32)
+            disp = predict_pair.result(tickets.pop(i))
         else:
             im0, im1 = pair_paths(path, action, i)
-            disp = np.asarray(predict_pair(im0, im1), np.float32)
+            disp = predict_pair(im0, im1)
+        if sparse:
+            disp, outlier = disp
+            outlier = np.asarray(outlier, np.float32)
+        disp = np.asarray(disp, np.float32)
         if action == "test":
             gt = read_png16("%s/training/disp_noc/%06d_10.png" % (path, i))
-            err = three_pixel_error(disp, gt)
+            if sparse:
+                err, density = sparse_error(disp, gt, outlier)
+                density_sum += density
+                log(i, err, density)
+            else:
+                err = three_pixel_error(disp, gt)
+                log(i, err)
             err_sum += err
-            log(i, err)
         else:
+            if sparse:
+                disp = np.where(outlier == 0, disp, np.float32(0))
             os.makedirs(out_dir, exist_ok=True)
             write_png16(disp, "%s/%06d_10.png" % (out_dir, i))
             log(i)
         done += 1
-    return err_sum, done
+    return (err_sum, done, density_sum) if sparse else (err_sum, done)
 
 
 class PairPipeline:
@@ -79,11 +107,12 @@ class PairPipeline:
     work of one pair and the GPU work of another overlap, and so do the kernels of two pairs (different streams).  The library is
     re-entrant: one workspace and one scratch area per stream."""
 
-    def __init__(self, prm, layers, disp_max, dev, slots=2, conv_mode="fp32"):
+    def __init__(self, prm, layers, disp_max, dev, slots=2, conv_mode="fp32", sparse=False):
         import concurrent.futures
         import torch
         self.prm, self.layers, self.disp_max, self.dev = prm, layers, disp_max, dev
         self.conv_mode = conv_mode          # main.features_fast's: mc_conv3x3 (fp32) or mc_conv_split (bf16x3) for the inner layers
+        self.sparse = sparse                # -sparse: a pair's result is (disparity, outlier classes), through mc_predict_ex
         self.slots = [dict(stream=torch.cuda.Stream(device=dev), shape=None) for _ in range(max(1, slots))]
         self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=len(self.slots))
         self.next = 0
@@ -106,13 +135,19 @@ class PairPipeline:
             H, W = host.shape[-2:]
             sl.update(shape=host.shape, pin_in=torch.empty(host.shape, dtype=torch.float32).pin_memory(),
                       pin_out=torch.empty((H, W), dtype=torch.float32).pin_memory(),
+                      pin_outlier=torch.empty((H, W), dtype=torch.float32).pin_memory() if self.sparse else None,
                       ws=Workspace(self.prm, self.disp_max, H, W, self.dev))
         sl["pin_in"].copy_(torch.from_numpy(host))
         with torch.cuda.stream(sl["stream"]):
             xb = sl["pin_in"].to(self.dev, non_blocking=True)
-            res = stereo_predict_fused(xb, self.prm, self.disp_max, feat=mcmain.features_fast(xb, self.layers, self.conv_mode), workspace=sl["ws"])
+            res = stereo_predict_fused(xb, self.prm, self.disp_max, feat=mcmain.features_fast(xb, self.layers, self.conv_mode), workspace=sl["ws"],
+                                       want_outlier=self.sparse)
             sl["pin_out"].copy_(res["disp"].reshape(xb.shape[2:]), non_blocking=True)
+            if self.sparse:
+                sl["pin_outlier"].copy_(res["outlier"].reshape(xb.shape[2:]), non_blocking=True)
         sl["stream"].synchronize()
+        if self.sparse:
+            return sl["pin_out"].numpy().copy(), sl["pin_outlier"].numpy().copy()
         return sl["pin_out"].numpy().copy()
 
     def submit(self, im0, im1):
@@ -138,6 +173,8 @@ def parse(argv=None):
     ap.add_argument("-disp_max", type=int, default=228)
     ap.add_argument("-n", type=int, default=None, help="number of pairs (default: the reference's 194 / 195)")
     ap.add_argument("-pairs_in_flight", type=int, default=2, help="pairs staged / queued ahead per rank (1: one at a time)")
+    ap.add_argument("-sparse", action="store_true",
+                    help="keep the pixels that passed the left-right check only: submit writes 0 elsewhere, test prints i err density")
     add_conv_mode_flag(ap)           # main.py's flag: the fast net's convolutions
     opt = ap.parse_args(argv)
     check_conv_mode(opt, "fast", "predict_kitti")
@@ -160,14 +197,18 @@ def main(argv=None):
     layers = mcmain.device_layers(mcmain.load_net(opt.net_fname, "kitti", "fast"), dev)   # resident: uploaded once
     prm = dict(TABLES[("kitti", "fast")])
     prm["border_n"] = len(layers)
-    predict_pair = PairPipeline(prm, layers, opt.disp_max, dev, slots=opt.pairs_in_flight, conv_mode=getattr(opt, "conv_mode", "fp32"))
-    err_sum, done = run(opt.action, opt.path, predict_pair, world, rank, n_pairs=opt.n, in_flight=opt.pairs_in_flight)
+    predict_pair = PairPipeline(prm, layers, opt.disp_max, dev, slots=opt.pairs_in_flight, conv_mode=getattr(opt, "conv_mode", "fp32"),
+                               sparse=opt.sparse)
+    sums = run(opt.action, opt.path, predict_pair, world, rank, n_pairs=opt.n, in_flight=opt.pairs_in_flight, sparse=opt.sparse)
     if opt.action == "test":
-        t = torch.tensor([err_sum, float(done)], dtype=torch.float64, device=dev)
+        err_sum, done = sums[:2]
+        t = torch.tensor([err_sum, float(done)] + list(sums[2:]), dtype=torch.float64, device=dev)
         if world > 1:
             dist.all_reduce(t)
         if rank == 0:
             print(t[0].item() / max(t[1].item(), 1.0))   # predict_kitti.lua:83
+            if opt.sparse:
+                print(t[2].item() / max(t[1].item(), 1.0))   # the mean density
     if world > 1:
         dist.destroy_process_group()
     return 0

@@ -74,7 +74,9 @@ int stereo_join_dhw(const float *fL, const float *fR, float *volL, float *volR, 
 // (banded) GEMM with K = C.  v_mfma_f32_32x32x2_f32 evaluates, per output element,
 // D = fma(a_k1, b_k1, fma(a_k0, b_k0, C)) (MI355X guide, "FP32-input MFMA": bit-for-bit a k-ordered
 // fmaf chain), so chaining the k-steps with c ascending reproduces StereoJoin_'s
-// `sum -= L*R` (adcensus.cu:1468-1471) bit for bit -- checked by tests/test_gpu_parity.py.
+// `sum -= L*R` (adcensus.cu:1468-1471) bit for bit -- held to the oracle voxel by voxel by tests/test_gpu_join_hwd.py, on the
+// hardware also where products or sums are subnormal (not flushed), where a product overflows on its own inside a finite
+// sum (exact inside the fma), and with +-0, +-inf and NaN operands, the zero-padded k-steps included.
 //
 // One wave owns 32 consecutive LEFT pixels x of one image row (M side, operand A = -L, held in VGPRs for
 // the whole band) and walks the right-image tiles x' = p0 - 32J .. (N side, operand B = R, prefetched one
@@ -332,7 +334,8 @@ __device__ __forceinline__ void join_owner_tiles(const float *__restrict__ fL, c
 		for (int pass = 0; pass < 4; ++pass) {
 			const int d0 = fd0[t][pass] + 32 * J;
 			const int fro = (pass * 8 + (lane >> 3)) * 64;
-			// (unsigned)d0 < ds  <=>  the piece holds at least one d of [0, D) of THIS pixel (d0 % 4 == 0, ds = D rounded up to 4)
+			// (unsigned)d0 < ds  <=>  the piece lies in THIS pixel's run (d0 % 4 == 0, ds % 4 == 0): with ds = D rounded up to 4 it holds at
+			// least one d of [0, D); a larger ds also stores the pieces of the padding [D, ds), out of whatever the ring holds there
 			const float4 v = *(const float4 *)(ring + fro + (d0 & 63));
 			__builtin_amdgcn_raw_buffer_store_b128((cb_u4_t){__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)},
 			                                       rrow, ((unsigned)d0 < (unsigned)ds) ? fgo[t][pass] + (unsigned)d0 * 4u : OOBF, 0, MC_JOIN_STORE_AUX);

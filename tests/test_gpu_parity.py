@@ -5,6 +5,7 @@ indices and the final sub-pixel map alike."""
 import numpy as np
 import pytest
 
+import join_cases as jc
 from util import (blocky_pair, diff_report, features, random_pair, raw_volumes, same_bits, smooth_pair)
 
 pytestmark = pytest.mark.gpu
@@ -40,6 +41,43 @@ def test_stereo_join(mc, oracle, H, W, D, C):
     mc.adcensus.StereoJoin(fd[0], fd[1], vl, vr)
     assert_same(host(vl), want_l, "volL")
     assert_same(host(vr), want_r, "volR")
+
+
+def join_dhw_into_poison(mc, f, D):
+    """mc_stereo_join into volumes poisoned with a NaN payload that no kernel writes: [volL, volR] as (D,H,W), on the host"""
+    _, H, W = f[0].shape
+    fd = dev(f.copy())   # (a copy: the shared features are read-only)
+    vols = [torch.full((1, D, H, W), jc.POISON, dtype=torch.int32, device="cuda").view(torch.float32) for _ in range(2)]
+    mc.adcensus.StereoJoin(fd[0], fd[1], vols[0], vols[1])
+    return [host(v)[0] for v in vols]
+
+
+def assert_join_dhw(got, want, D, W, what):
+    """the voxels with a partner pixel equal the oracle; those the reference leaves to the caller's fill are still poison"""
+    for g, w, live, name in ((got[0], want[0], jc.live_left(D, W).T, "volL"), (got[1], want[1], jc.live_right(D, W).T, "volR")):
+        live = np.broadcast_to(live[:, None, :], g.shape)    # (D, W) -> (D, H, W)
+        assert not np.isnan(w[live]).any() and np.isnan(w[~live]).all()
+        assert not (g.view(np.int32)[live] == jc.POISON).any(), "%s %s: live voxels were not written" % (what, name)
+        assert_same(g[live], w[live], "%s %s" % (what, name))
+        assert (g.view(np.int32)[~live] == jc.POISON).all(), "%s %s: a voxel without a partner pixel was written" % (what, name)
+
+
+@pytest.mark.parametrize("C", jc.DHW_C)
+def test_stereo_join_channels_and_tile_edges(mc, oracle, C):
+    """join_dhw_kernel: channels around its staging chunk of 16 and at the limit, W and D on both sides of its 64 x 32 block"""
+    for H, W, D in jc.DHW_SHAPES:
+        f = jc.feats("unit", C, H, W)
+        assert_join_dhw(join_dhw_into_poison(mc, f, D), oracle.stereo_join(f[0], f[1], D), D, W, "C=%d H=%d W=%d D=%d" % (C, H, W, D))
+
+
+@pytest.mark.parametrize("recipe,C,shape", jc.DHW_VALUES)
+def test_stereo_join_value_ranges(mc, oracle, recipe, C, shape):
+    """subnormal products and sums; sums that overflow (no NaN: the product inside an fma is exact) -- tests/test_join_cases_host.py"""
+    H, W, D = shape
+    f = jc.feats(recipe, C, H, W)
+    with np.errstate(all="ignore"):
+        want = oracle.stereo_join(f[0], f[1], D)
+    assert_join_dhw(join_dhw_into_poison(mc, f, D), want, D, W, "%s C=%d" % (recipe, C))
 
 
 @pytest.mark.parametrize("H,W,D", SHAPES[:4])

@@ -277,6 +277,28 @@ int mc_predict_ex(const mc_params *p, const float *x0, const float *x1,
                   float *outlier_out, float *cost_out, float *curv_out,
                   float *disp_out, void *stream);
 
+/* mc_predict_ex with the RIGHT view's finished map: two more optional (H,W) outputs; with both NULL it IS mc_predict_ex: the same
+ * launches, the same bits.  Let M mirror a map along x, M(a)[y, x] = a[y, W-1-x].  Mirroring the scene turns the right image into a left
+ * one, so the right view's result is what the post-processing gives on the mirrored maps, mirrored back:
+ *   outlierR_out  M(oR) for oR = outlier_detection(M(dispR0), M(dispL0), D): the right view's classes, 0 match, 1 occlusion, 2 mismatch.
+ *                 Written whenever both arg-min maps exist, like outlier_out.
+ *   dispR_out     M(t) for t = M(dispR0) taken through interpolate_occlusion(t, oR), interpolate_mismatch(t, oR) (lr_check = 1 only),
+ *                 subpixel_enchancement(t, M(volR)) on the final right volume (what volR_out holds), median2d and mean2d -- every stage
+ *                 the left view's operator, dropped by sm_skip / sm_terminate exactly as on the left.
+ * The direction-dependent stages (the LR check's x - d, the occlusion stage's "look left first", the rounding of the mismatch stage's
+ * half-pixel rays, which is not mirror-symmetric) are fixed by the mirror; there is no separately defined right-handed variant.
+ * Asking for either map counts as a right-side output: left_only is ignored and both volumes are computed.  The workspace is
+ * mc_predict's; the added work is the (H,W) tail alone, on `stream` behind the left view's.
+ * MC_EINVAL, before anything is launched or written: what mc_predict_ex refuses; either map overlapping another output or the workspace. */
+int mc_predict_views(const mc_params *p, const float *x0, const float *x1,
+                     const float *featL, const float *featR, int C,
+                     const float *rawL, const float *rawR, int D, int H, int W,
+                     void *workspace, size_t workspace_bytes,
+                     float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out,
+                     float *outlier_out, float *cost_out, float *curv_out,
+                     float *dispR_out, float *outlierR_out,
+                     float *disp_out, void *stream);
+
 /* Timing hook for bench.py: the same pipeline with HIP events recorded on `stream`
  * at the stage boundaries of this call.  stage_ms[MC_N_STAGES] receives the summed
  * duration (ms) of each stage; the call synchronises the stream to read them. */

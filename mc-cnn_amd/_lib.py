@@ -18,7 +18,7 @@ SYMBOLS = [
     "mc_cross", "mc_cbca", "mc_cbca_scratch_bytes", "mc_cbca_ws", "mc_sgm2_tmp_bytes", "mc_sgm2", "mc_dhw_to_hwd", "mc_hwd_to_dhw", "mc_scale",
     "mc_argmin", "mc_spatial_argmin", "mc_outlier_detection", "mc_interpolate_occlusion",
     "mc_interpolate_mismatch", "mc_subpixel_enchancement", "mc_median2d", "mc_mean2d", "mc_gaussian_host",
-    "mc_normalize_forward", "mc_predict_workspace_bytes", "mc_predict_workspace_bytes_full", "mc_predict", "mc_predict_ex", "mc_predict_timed",
+    "mc_normalize_forward", "mc_predict_workspace_bytes", "mc_predict_workspace_bytes_full", "mc_predict", "mc_predict_ex", "mc_predict_views", "mc_predict_timed",
     "mc_cbca_plan_bytes", "mc_cbca_ws_cfg", "mc_transpose_cfg",
     "mc_read_png16", "mc_write_png16", "mc_write_pfm", "mc_grey2jet", "mc_sgm2_contract_violations",
 ]
@@ -78,6 +78,7 @@ def _load():
         "mc_normalize_forward": [vp, vp, vp, i, i, i, i, vp],
         "mc_predict": [C.POINTER(McParams), vp, vp, vp, vp, i, vp, vp, i, i, i, vp, sz, vp, vp, vp, vp, vp, vp],
         "mc_predict_ex": [C.POINTER(McParams), vp, vp, vp, vp, i, vp, vp, i, i, i, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "mc_predict_views": [C.POINTER(McParams), vp, vp, vp, vp, i, vp, vp, i, i, i, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "mc_predict_timed": [C.POINTER(McParams), vp, vp, vp, vp, i, vp, vp, i, i, i, vp, sz, vp, vp,
                              C.POINTER(C.c_float)],
         "mc_cbca_ws_cfg": [vp, vp, vp, vp, i, i, i, i, vp, sz, i, i, i, i, i, vp],

@@ -425,6 +425,19 @@ int mc_predict_ex(const mc_params *p, const float *x0, const float *x1, const fl
 	                    dispL0_out, dispR0_out, disp_out, as_stream(stream), tm, ex);
 }
 
+int mc_predict_views(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,
+                     const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
+                     float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out, float *outlier_out, float *cost_out, float *curv_out,
+                     float *dispR_out, float *outlierR_out, float *disp_out, void *stream)
+{
+	StageTimer tm;
+	PredictExtras ex;
+	ex.outlier = outlier_out; ex.cost = cost_out; ex.curv = curv_out;
+	ex.dispR = dispR_out; ex.outlierR = outlierR_out;
+	return predict_impl(p, x0, x1, featL, featR, C, rawL, rawR, D, H, W, workspace, workspace_bytes, volL_out, volR_out,
+	                    dispL0_out, dispR0_out, disp_out, as_stream(stream), tm, ex);
+}
+
 int mc_predict_timed(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,
                      const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
                      float *disp_out, void *stream, float *stage_ms)

@@ -26,6 +26,11 @@ int subpixel(const float *d0, const float *vol, float *out, int D, int H, int W,
 // arguments on subpixel: the host checks of predict.hip define subpixel as it stands above.)
 int subpixel_conf(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st, float *cost_out,
                   float *curv_out);
+// The mirror M of mc_predict_views, out[y, W-1-x] = in[y, x] (scale_kernel's mirrored form; in and out must not overlap), and the sub-pixel stage
+// on M(vol) without a mirrored volume: out[y, x] from d0[y, x] and the costs of pixel (y, W-1-x) (subpixel_kernel's mirrored form).  Names of
+// their own for the reason given above: predict.hip re-declares the two weak and refuses a right view without them.
+int mirror_rows(const float *in, float *out, int H, int W, hipStream_t st);
+int subpixel_mirrored(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st);
 int median2d(const float *img, float *out, int H, int W, int k, hipStream_t st);
 int mean2d(const float *img, const float *kernel, float *out, int H, int W, int ks, float alpha2, hipStream_t st);
 int normalize_forward(const float *in, float *norm, float *out, int N, int C, int H, int W, hipStream_t st);
@@ -135,7 +140,8 @@ struct StageTimer {   // mc_predict_timed: an event at every stage boundary
 };
 // mc_predict_ex's optional (H,W) maps: the LR check's classes (0 match, 1 occlusion, 2 mismatch), and the sub-pixel stage's cost at the
 // disparity it reads and the curvature of the cost curve there
-struct PredictExtras { float *outlier = nullptr, *cost = nullptr, *curv = nullptr; };
+// ... and mc_predict_views' two (H,W) maps of the RIGHT view: its finished disparity map and its classes (predict.hip, the right tail)
+struct PredictExtras { float *outlier = nullptr, *cost = nullptr, *curv = nullptr, *dispR = nullptr, *outlierR = nullptr; };
 int predict_impl(const mc_params *p, const float *x0, const float *x1, const float *featL, const float *featR, int C,
                  const float *rawL, const float *rawR, int D, int H, int W, void *workspace, size_t workspace_bytes,
                  float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out, float *disp_out, hipStream_t st,

@@ -14,8 +14,17 @@ __global__ void __launch_bounds__(256) fill_nan_kernel(float *__restrict__ p, in
 	for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = nanv;
 }
 
-__global__ void __launch_bounds__(256) scale_kernel(const float *__restrict__ in, float *__restrict__ out, int64_t n, float s)
+// mw (uniform over the grid: one scalar branch): 0 is the plain copy; mw > 0 takes the n values as rows of mw and writes each row mirrored,
+// out[y, mw-1-x] = in[y, x] * s -- the M of mc_predict_views (mirror_rows below).  The division by the row width sits behind the flag alone.
+__global__ void __launch_bounds__(256) scale_kernel(const float *__restrict__ in, float *__restrict__ out, int64_t n, float s, int mw)
 {
+	if (mw > 0) {
+		for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+			const int64_t x = i % mw;
+			out[i - x + (mw - 1 - x)] = in[i] * s;
+		}
+		return;
+	}
 	for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = in[i] * s;
 }
 // ... ONE 16-byte element per thread, blocks in address order: the form in which a copy streams fastest on this chip (6.3 TB/s at
@@ -110,8 +119,19 @@ int scale(const float *in, float *out, int64_t n, float s, hipStream_t st)
 		return check_launch("scale");
 	}
 	const unsigned blocks = cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u;
-	hipLaunchKernelGGL(scale_kernel, dim3(blocks), dim3(256), 0, st, in, out, n, s);
+	hipLaunchKernelGGL(scale_kernel, dim3(blocks), dim3(256), 0, st, in, out, n, s, 0);
 	return check_launch("scale");
+}
+
+// out[y, W-1-x] = in[y, x] for an (H,W) map: scale_kernel's mirrored form, one dword per lane (a mirrored 16-byte run would have to be
+// reversed in registers and lands unaligned wherever W % 4 != 0).  in and out must not overlap.
+int mirror_rows(const float *in, float *out, int H, int W, hipStream_t st)
+{
+	const int64_t n = (int64_t)H * W;
+	if (n <= 0) return 0;
+	const unsigned blocks = cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u;
+	hipLaunchKernelGGL(scale_kernel, dim3(blocks), dim3(256), 0, st, in, out, n, 1.0f, W);
+	return check_launch("mirror_rows");
 }
 
 int transpose(const float *in, float *out, int64_t R, int64_t Cn, int64_t ldin, int64_t ldout, float s, hipStream_t st, int nt)
@@ -592,14 +612,20 @@ int interpolate_mismatch(const float *d0, const float *outlier, float *out, int 
 // cost_out / curv_out (mc_predict_ex, either may be null): the two confidence measures the stage has in its hands, c(d) and the
 // curvature 2 (cp + cn - 2 cz) of the cost curve at d -- `denom` itself; 0 where the stage reads no neighbours.  Both null: the
 // kernel loads and stores what it always did.  Only cost_out adds a load, of c(d) at d = 0 and d = disp_max - 1.
+// mw (uniform over the grid; mc_predict_views' right view): 0 reads pixel id's costs; mw > 0 takes the maps as rows of mw pixels and reads
+// the costs of the MIRRORED pixel (y, mw-1-x) -- the stage on M(vol) without a mirrored volume; cost_out / curv_out are then null.
 __global__ void __launch_bounds__(256) subpixel_kernel(const float *__restrict__ d0, const float *__restrict__ c2,
                                                        float *__restrict__ out, int64_t size, int64_t sd, int64_t sp, int disp_max,
-                                                       float *__restrict__ cost_out, float *__restrict__ curv_out)
+                                                       float *__restrict__ cost_out, float *__restrict__ curv_out, int mw)
 {
 	const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (id >= size) return;
 	const int d = (int)d0[id];
 	float res = (float)d;
+	if (mw > 0) {
+		const int64_t x = id % mw;
+		c2 += (id - x + (mw - 1 - x)) * sp - id * sp;   // (the reads below add id * sp)
+	}
 	if (1 <= d && d < disp_max - 1) {
 		const float cn = c2[(d - 1) * sd + id * sp];
 		const float cz = c2[d * sd + id * sp];
@@ -622,8 +648,16 @@ int subpixel_conf(const float *d0, const float *vol, float *out, int D, int H, i
                   float *curv_out)
 {
 	const int64_t size = (int64_t)H * W;
-	hipLaunchKernelGGL(subpixel_kernel, dim3(cdiv(size, 256)), dim3(256), 0, st, d0, vol, out, size, sd, sp, D, cost_out, curv_out);
+	hipLaunchKernelGGL(subpixel_kernel, dim3(cdiv(size, 256)), dim3(256), 0, st, d0, vol, out, size, sd, sp, D, cost_out, curv_out, 0);
 	return check_launch("subpixel_enchancement");
+}
+
+// subpixel on the mirrored volume: out[y, x] from d0[y, x] and the costs of pixel (y, W-1-x)
+int subpixel_mirrored(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st)
+{
+	const int64_t size = (int64_t)H * W;
+	hipLaunchKernelGGL(subpixel_kernel, dim3(cdiv(size, 256)), dim3(256), 0, st, d0, vol, out, size, sd, sp, D, (float *)nullptr, (float *)nullptr, W);
+	return check_launch("subpixel_enchancement (mirrored)");
 }
 
 int subpixel(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st)

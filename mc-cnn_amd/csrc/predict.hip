@@ -17,6 +17,9 @@ int sgm_prep_d(const float *x0, const float *x1, void *maps, int H, int W, int D
 // no call of theirs asks for a map.  Without it such a call is refused (predict_impl).
 int subpixel_conf(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st, float *cost_out,
                   float *curv_out) __attribute__((weak));
+// ... and the two mirrored forms of mc_predict_views' right tail (post.hip): without them a right-view map is refused (predict_impl).
+int mirror_rows(const float *in, float *out, int H, int W, hipStream_t st) __attribute__((weak));
+int subpixel_mirrored(const float *d0, const float *vol, float *out, int D, int H, int W, int64_t sd, int64_t sp, hipStream_t st) __attribute__((weak));
 
 // gaussian(sigma), main.lua:528-540, double on the host.  mc_predict reads it from DEVICE memory, cached per (device, sigma): allocated and
 // uploaded synchronously at first use (complete before any stream can be given it) and never freed; it depends on the preset alone.
@@ -272,6 +275,14 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 		auto overlap = [](const Range &a, const Range &b) {
 			return a.at && b.at && (uintptr_t)a.at < (uintptr_t)b.at + b.bytes && (uintptr_t)b.at < (uintptr_t)a.at + a.bytes;
 		};
+		// mc_predict_views' two maps of the right view: the same range check
+		const Range views[2] = {{"dispR_out", ex.dispR, map_bytes}, {"outlierR_out", ex.outlierR, map_bytes}};
+		for (int i = 0; i < 2; ++i) {
+			if (views[i].at) MC_REQUIRE(mirror_rows && subpixel_mirrored, "mc_predict_views: %s needs the mirrored kernels, which this program does not link", views[i].name);
+			for (const Range &o : others) MC_REQUIRE(!overlap(views[i], o), "mc_predict_views: %s overlaps %s", views[i].name, o.name);
+			for (const Range &o : extras) MC_REQUIRE(!overlap(views[i], o), "mc_predict_views: %s overlaps %s", views[i].name, o.name);
+			for (int j = 0; j < i; ++j) MC_REQUIRE(!overlap(views[i], views[j]), "mc_predict_views: %s overlaps %s", views[i].name, views[j].name);
+		}
 		for (int i = 0; i < 3; ++i) {
 			if (i > 0 && extras[i].at) {
 				MC_REQUIRE(sc.subpixel, "mc_predict_ex: %s is written by the sub-pixel stage, which sm_terminate=%d / sm_skip=%d leave out",
@@ -316,7 +327,8 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 	bool hwd;  // layout of cur[]
 	// direction +1 (the right volume) is skipped where the reference skips it: dataset mb outside `-a predict`
 	// (mb_directions, main.lua:953-955) -- only when nothing of it is asked for (the class map compares the two arg-min maps)
-	const int nvol = (p->left_only && !p->lr_check && !volR_out && !dispR0_out && !ex.outlier) ? 1 : 2;
+	const bool right_view = ex.dispR || ex.outlierR;   // mc_predict_views: the tail runs a second time, on the right view (below)
+	const int nvol = (p->left_only && !p->lr_check && !volR_out && !dispR0_out && !ex.outlier && !right_view) ? 1 : 2;
 	// n CBCA iterations on the (D,H,W) volumes, ping-pong between the two buffers of each side (instead of vol:copy(tmp)).
 	// Where the pair's route may be the texture one (cfg.lean), the iterations go in PAIRS: cbca_lean2x runs two passes in one launch
 	// (cur -> dst) out of a list written once per pair and direction; the kernels of the other routes -- which one runs is decided on
@@ -386,7 +398,8 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 			// left volume, the LR check the arg-min maps that the up sweep writes regardless) -- not stored unless asked for.
 			// sgm_sweeps counts its bits from the first volume it is given: bit 1 of a pair, bit 0 of the right volume alone
 			const bool has_right = v0 + nv == 2;
-			const unsigned drop_final = (am && has_right && !volR_out) ? 1u << (1 - v0) : 0u;
+			// (... and the right view's sub-pixel stage, where its map is asked for)
+			const unsigned drop_final = (am && has_right && !volR_out && !(ex.dispR && sc.subpixel)) ? 1u << (1 - v0) : 0u;
 			const int rc1 = have_ck ? sgm_sweeps_ck(Cv, outv, scratch, am ? dv : nullptr, dir, nv, H, W, D, ds, pl.maps, p->pi1, p->pi2, p->alpha1,
 			                                        p->sgm_q1, p->sgm_q2, true, drop_final, nan_triangle, ckv, s)
 			                        : sgm_sweeps(Cv, outv, scratch, am ? dv : nullptr, dir, nv, H, W, D, ds, pl.maps, p->pi1, p->pi2, p->alpha1,
@@ -547,6 +560,60 @@ int predict_impl(const mc_params *p, const float *x0, const float *x1, const flo
 		RUN(mean2d(d, gk, disp_out, H, W, gaussian_ks(p->blur_sigma), p->blur_t, st));
 	} else {
 		RUN(scale(d, disp_out, HW, 1.0f, st));  // the last stage that ran is the result
+	}
+
+	// ---- (D) mc_predict_views: the same tail on the RIGHT view ----
+	// Mirroring the scene along x, M(a)[y, x] = a[y, W-1-x], turns the right image into a left one, so the right view's map is what the tail
+	// above gives on the mirrored maps, mirrored back: the classes from (M(dispR0), M(dispL0)), the two interpolations, the sub-pixel stage
+	// on M(volR), median, blur.  The direction-dependent stages -- the LR check's x - d, the occlusion stage's "look left first" and the
+	// roundf of the half-step mismatch rays, which is NOT mirror-symmetric -- are thereby fixed by the mirror: the kernels are the left
+	// view's, fed physically mirrored maps, and no right-handed variant of any of them exists.  Only the sub-pixel stage, which is
+	// pointwise, reads the volume at the mirrored pixel instead of a mirrored volume (the mean's float sum runs in tap order and does not
+	// commute with M, so it is not given M's output but M's input, like the others).
+	// The workspace: the left tail is done, so of the six images only the arg-min maps 0 and 1 are live, and they die with the two
+	// mirrored copies (into 2 and 3).  The classes go to 4 (the left view's are in the caller's map or no longer read), the stages rotate
+	// through 0, 1, 5 and, once the classes are computed, 3.  The right volume cur[1] is whole: nothing above writes a volume behind the
+	// arg-min (the left tail writes images, the caller's maps and the mismatch bitmask in the cross arms' area), the two-lane path has
+	// joined, and drop_final keeps the final costs where this map is asked for.
+	if (right_view) {
+		float *const mR = pl.img[2], *const mL = pl.img[3], *const oR = pl.img[4];
+		RUN(mirror_rows(dispv[1], mR, H, W, st));
+		RUN(mirror_rows(dispv[0], mL, H, W, st));
+		RUN(outlier_detection(mR, mL, oR, H, W, D, st));
+		if (ex.outlierR) RUN(mirror_rows(oR, ex.outlierR, H, W, st));
+		if (ex.dispR) {
+			d = mR;
+			float *const rimg[4] = {pl.img[0], pl.img[1], pl.img[5], pl.img[3]};
+			int nr = 0;
+			auto rstage = [&](bool runs, auto &&run) -> int {
+				if (runs) {
+					float *o = rimg[nr++ % 4];
+					if (const int rc1 = run(o)) return rc1;
+					d = o;
+				}
+				return 0;
+			};
+			if (p->lr_check) {
+				const unsigned *mis_mask = nullptr;
+				RUN(rstage(sc.occlusion, [&](float *o) {
+					unsigned *m = HW <= MC_MIS_MASK_MAX_PIXELS ? (unsigned *)pl.x0c : nullptr;
+					mis_mask = m;
+					return interpolate_occlusion(d, oR, o, H, W, st, m);
+				}));
+				RUN(rstage(sc.mismatch, [&](float *o) { return interpolate_mismatch(d, oR, o, H, W, st, mis_mask); }));
+			}
+			RUN(rstage(sc.subpixel, [&](float *o) {
+				const int64_t sd = hwd ? 1 : HW, sp = hwd ? ds : 1;
+				return subpixel_mirrored(d, cur[1], o, D, H, W, sd, sp, st);
+			}));
+			RUN(rstage(sc.median, [&](float *o) { return median2d(d, o, H, W, p->median_k, st); }));
+			if (sc.bilateral) {
+				const float *gk = nullptr;
+				RUN(gaussian_cached(p->blur_sigma, gk));
+				RUN(rstage(true, [&](float *o) { return mean2d(d, gk, o, H, W, gaussian_ks(p->blur_sigma), p->blur_t, st); }));
+			}
+			RUN(mirror_rows(d, ex.dispR, H, W, st));
+		}
 	}
 	tm.mark(MC_STAGE_POST);
 #undef RUN

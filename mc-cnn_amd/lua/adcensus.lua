@@ -88,6 +88,14 @@ int mc_predict_ex(const mc_params *p, const float *x0, const float *x1,
                   float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out,
                   float *outlier_out, float *cost_out, float *curv_out,
                   float *disp_out, void *stream);
+int mc_predict_views(const mc_params *p, const float *x0, const float *x1,
+                     const float *featL, const float *featR, int C,
+                     const float *rawL, const float *rawR, int D, int H, int W,
+                     void *workspace, size_t workspace_bytes,
+                     float *volL_out, float *volR_out, float *dispL0_out, float *dispR0_out,
+                     float *outlier_out, float *cost_out, float *curv_out,
+                     float *dispR_out, float *outlierR_out,
+                     float *disp_out, void *stream);
 int mc_read_png16(const char *fname, float *img, int64_t capacity, int *height, int *width);
 int mc_write_png16(const float *img, int height, int width, const char *fname);
 int mc_write_pfm(const float *img, int height, int width, const char *fname);
@@ -296,6 +304,9 @@ end
 --            the final left volume at the disparity the sub-pixel stage reads, and the curvature 2 (c[d+1] + c[d-1] - 2 c[d]) of the
 --            cost curve there (0 at d = 0 and d = disp_max - 1).  cost / curvature with -sm_skip subpixel_enchancement, or a
 --            -sm_terminate in front of that stage, is an error.  Without the table the call is mc_predict.
+--            Two more keys, disp_right= and outlier_right=, ask for the RIGHT view's finished map and classes (mc_predict_views): the
+--            post-processing on the x-mirrored arg-min maps and right volume, mirrored back, for the price of that tail alone; both
+--            volumes are then computed whatever `both` says.
 -- Returns disp (1,1,H,W) and, when `both`, volL, volR (1,disp_max,H,W).
 local SM_TERMINATE = {[''] = 0, cnn = 1, cbca1 = 2, sgm = 3, cbca2 = 4, occlusion = 5, mismatch = 6,
                       subpixel_enchancement = 7, median = 8, bilateral = 9}
@@ -335,7 +346,7 @@ function adcensus.predict(o, dataset, arch, x_batch, input, disp_max, border_n, 
       return disp, volL, volR
    end
    local ex = {}
-   for _, k in ipairs({'outlier', 'cost', 'curvature'}) do
+   for _, k in ipairs({'outlier', 'cost', 'curvature', 'disp_right', 'outlier_right'}) do
       local t = extras[k]
       if t ~= nil then
          if torch.typename(t) ~= 'torch.CudaTensor' then
@@ -345,7 +356,14 @@ function adcensus.predict(o, dataset, arch, x_batch, input, disp_max, border_n, 
       end
    end
    for k in pairs(extras) do
-      if k ~= 'outlier' and k ~= 'cost' and k ~= 'curvature' then error('predict: unknown extra ' .. tostring(k), 2) end
+      if k ~= 'outlier' and k ~= 'cost' and k ~= 'curvature' and k ~= 'disp_right' and k ~= 'outlier_right' then
+         error('predict: unknown extra ' .. tostring(k), 2)
+      end
+   end
+   if ex.disp_right ~= nil or ex.outlier_right ~= nil then
+      check(lib.mc_predict_views(p, x0, x1, fl, fr, C, rl, rr, disp_max, H, W, ws, need, pl, pr, nil, nil, ex.outlier, ex.cost, ex.curvature,
+                                 ex.disp_right, ex.outlier_right, disp:data(), nil), 'predict')
+      return disp, volL, volR
    end
    check(lib.mc_predict_ex(p, x0, x1, fl, fr, C, rl, rr, disp_max, H, W, ws, need, pl, pr, nil, nil, ex.outlier, ex.cost, ex.curvature,
                            disp:data(), nil), 'predict')

@@ -9,7 +9,9 @@ convolutions are `mc_conv3x3`, a hand-written fp32-MFMA implicit GEMM of libmcad
 pipeline in one `mc_predict` call, and writes `left.bin`, `right.bin` (1,D,H,W) and `disp.bin` (1,1,H,W), raw float32,
 with the reference's messages.  `-a time` is main.lua:1140-1167 (min of N runs on an uninitialised batch).  `-a predict -extras` also
 writes `outlier.bin`, `cost.bin` and `curvature.bin` (1,1,H,W) next to `disp.bin`: the LR check's class of every pixel (0 match, 1 occlusion,
-2 mismatch) and the two confidence measures of the sub-pixel stage (`mc_predict_ex`; no counterpart in main.lua).
+2 mismatch) and the two confidence measures of the sub-pixel stage (`mc_predict_ex`; no counterpart in main.lua).  `-a predict -right_view`
+also writes `disp_right.bin` (1,1,H,W), the RIGHT view's finished disparity map -- the post-processing on the x-mirrored arg-min maps and
+right volume, mirrored back (`mc_predict_views`) -- and, with `-extras`, its classes as `outlier_right.bin`.
 
 Architectures: fast, slow (feature net + `mc_fc_stack`, main.lua:958-983; `-fc_mode bf16x3` takes the FC stack's products as three
 bf16 products each, `mc_fc_split_stack` of libmcfcsplit.so, wherever arch slow predicts; the default `-fc_mode fp32` is `mc_fc_stack`;
@@ -100,6 +102,8 @@ def parse(argv):
     ap.add_argument("-disp_max", type=int, default=228 if dataset != "mb" else 200)
     ap.add_argument("-tiny", action="store_true")
     ap.add_argument("-extras", action="store_true", help="-a predict: also write outlier.bin, cost.bin and curvature.bin (mc_predict_ex)")
+    ap.add_argument("-right_view", action="store_true",
+                    help="-a predict: also write disp_right.bin, the right view's finished disparity map (mc_predict_views); with -extras also outlier_right.bin")
     add_fc_mode_flag(ap)
     add_conv_mode_flag(ap)
     ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
@@ -122,6 +126,8 @@ def parse(argv):
                          % (opt.a, dataset, arch, " | ".join(TRAIN_ACTIONS)))
     if opt.extras and opt.a != "predict":
         raise SystemExit("main.py: -extras writes outlier.bin, cost.bin and curvature.bin next to disp.bin and goes with -a predict only")
+    if opt.right_view and opt.a != "predict":
+        raise SystemExit("main.py: -right_view writes disp_right.bin next to disp.bin and goes with -a predict only")
     if getattr(opt, "at", 0) == 1 and opt.data_dir:
         raise SystemExit("main.py: -at 1 reads data.kitti and data.kitti2015 together (main.lua:403-426) and takes no -data_dir")
     return dataset, arch, opt, pipeline_prm(t, opt)
@@ -289,8 +295,10 @@ def main(argv=None):
     prm["border_n"] = len(layers)  # (1 + l1*(3-1) - 1) / 2, main.lua:382-391,923
     conv_mode = getattr(opt, "conv_mode", "fp32")   # the feature net's convolutions wherever this command line predicts
 
-    def run(x_batch, D, workspace=None, want_volumes=False, extras=False):
+    def run(x_batch, D, workspace=None, want_volumes=False, extras=False, right_view=False):
         more = dict(want_outlier=True, want_confidence=True) if extras else {}   # -extras: mc_predict_ex's three maps
+        if right_view:                                                          # -right_view: mc_predict_views' two
+            more["want_right"] = True
         if not learned:  # main.lua:932-942: hand-crafted costs straight from the image pair, no border fix
             from . import adcensus
             cost = adcensus.ad if arch == "ad" else adcensus.census
@@ -345,7 +353,7 @@ def main(argv=None):
         x0, x1 = rgb2y(x0), rgb2y(x1)
     D = opt.disp_max
     x_batch = torch.from_numpy(np.stack([normalize(x0), normalize(x1)])).to(dev)  # (2,1,H,W)
-    res = run(x_batch, D, want_volumes=True, extras=opt.extras)
+    res = run(x_batch, D, want_volumes=True, extras=opt.extras, right_view=opt.right_view)
     torch.cuda.synchronize()
     H, W = x_batch.shape[2:]
     for name, key in (("right", "volR"), ("left", "volL")):  # main.lua:954-955 writes right.bin first
@@ -357,6 +365,10 @@ def main(argv=None):
         for name, key in (("outlier", "outlier"), ("cost", "cost"), ("curvature", "curvature")):
             print("Writing %s.bin, %d x %d x %d x %d" % (name, 1, 1, H, W))
             write_bin("%s.bin" % name, res[key].cpu().numpy())
+    if opt.right_view:
+        for name in ("disp_right",) + (("outlier_right",) if opt.extras else ()):
+            print("Writing %s.bin, %d x %d x %d x %d" % (name, 1, 1, H, W))
+            write_bin("%s.bin" % name, res[name].cpu().numpy())
     return 0
 
 

@@ -40,7 +40,8 @@ def stereo_predict(x_batch, params, disp_max, feat=None, raw=None, return_all=Fa
     intermediate maps and the three per-pixel maps of mc_predict_ex: `outlier`
     (the LR check's classes; without the LR check it runs for the map alone),
     `cost` and `curvature` (the left volume around the disparity the sub-pixel
-    stage reads), each (1,1,H,W)."""
+    stage reads), each (1,1,H,W), and the two maps of mc_predict_views,
+    `disp_right` and `outlier_right` (right_view below)."""
     p = make_params(params)
     x0, x1, H, W = _img2(x_batch)
     D = int(disp_max)
@@ -101,9 +102,31 @@ def stereo_predict(x_batch, params, disp_max, feat=None, raw=None, return_all=Fa
     d = adcensus.median2d(d, p.median_k)
     d = adcensus.mean2d(d, adcensus.gaussian(p.blur_sigma).to(dev), p.blur_t)
     if return_all:
+        disp_right, outlier_right = right_view(p, disp[2], disp[1], out_vols[1], D)
         return dict(disp=d, volL=out_vols[-1], volR=out_vols[1], dispL0=disp[2], dispR0=disp[1], outlier=outlier, cost=cost,
-                    curvature=curvature)
+                    curvature=curvature, disp_right=disp_right, outlier_right=outlier_right)
     return d
+
+
+def right_view(p, dispL0, dispR0, volR, D):
+    """mc_predict_views' dispR_out and outlierR_out with the stand-alone operators and torch.flip.  Mirroring the scene along x turns
+    the right image into a left one, so the right view's map is the post-processing above on the mirrored arg-min maps and the
+    mirrored right volume, mirrored back; the stages follow the parameter set's lr_check as above.  (The direction-dependent
+    stages -- the LR check's x - d, the occlusion stage's look to the left, the rounding of the mismatch rays' half steps -- are
+    the left view's on mirrored data: that IS the definition.)  Returns (disp_right, outlier_right), (1,1,H,W) each."""
+    def M(a):
+        return torch.flip(a, dims=[-1]).contiguous()
+
+    t = M(dispR0)
+    outlier = torch.zeros_like(t)
+    adcensus.outlier_detection(t, M(dispL0), outlier, D)
+    if p.lr_check:
+        t = adcensus.interpolate_occlusion(t, outlier)
+        t = adcensus.interpolate_mismatch(t, outlier)
+    t = adcensus.subpixel_enchancement(t, M(volR), D)
+    t = adcensus.median2d(t, p.median_k)
+    t = adcensus.mean2d(t, adcensus.gaussian(p.blur_sigma).to(t.device), p.blur_t)
+    return M(t), M(outlier)
 
 
 def confidence_maps(d, vol):
@@ -142,12 +165,15 @@ class Workspace:
 
 
 def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspace=None, want_volumes=False,
-                         want_disp0=False, out=None, timed=False, want_outlier=False, want_confidence=False):
+                         want_disp0=False, out=None, timed=False, want_outlier=False, want_confidence=False, want_right=False):
     """The whole of stereo_predict from the cost-volume stage on, in one C-ABI call.
 
     want_outlier adds res["outlier"], the LR check's class per pixel (0 match, 1 occlusion, 2 mismatch); want_confidence adds
     res["cost"] and res["curvature"], the final left volume at the disparity the sub-pixel stage reads and the curvature of the cost
-    curve there.  Each is (1,1,H,W); with either flag the call is mc_predict_ex, otherwise mc_predict."""
+    curve there.  Each is (1,1,H,W); with either flag the call is mc_predict_ex, otherwise mc_predict.
+
+    want_right adds res["disp_right"] and res["outlier_right"], the right view's finished disparity map and its classes (right_view
+    above states them op by op); the call is then mc_predict_views, and the right view costs the (H,W) tail alone."""
     p = make_params(params)
     x0, x1, H, W = _img2(x_batch)
     D = int(disp_max)
@@ -184,7 +210,14 @@ def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspa
         res["dispL0"] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
         res["dispR0"] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
         dl, dr = res["dispL0"].data_ptr(), res["dispR0"].data_ptr()
-    if want_outlier or want_confidence:
+    if want_right:
+        names = (("outlier",) if want_outlier else ()) + (("cost", "curvature") if want_confidence else ()) + ("disp_right", "outlier_right")
+        for name in names:
+            res[name] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
+        ex = [res[name].data_ptr() if name in res else None for name in ("outlier", "cost", "curvature", "disp_right", "outlier_right")]
+        check(lib.mc_predict_views(C.byref(p), x0.data_ptr(), x1.data_ptr(), fl, fr, Cn, rl, rr, D, H, W, workspace.ptr,
+                                   ws_bytes, vl, vr, dl, dr, ex[0], ex[1], ex[2], ex[3], ex[4], out.data_ptr(), st), "mc_predict_views")
+    elif want_outlier or want_confidence:
         names = (("outlier",) if want_outlier else ()) + (("cost", "curvature") if want_confidence else ())
         for name in names:
             res[name] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)

@@ -164,6 +164,19 @@ int mc_argmin(const float *vol, float *disp, int D, int H, int W, void *stream);
 /* adcensus.spatial_argmin(input, output), adcensus.cu:264-278: 1-based. */
 int mc_spatial_argmin(const float *vol, float *out, int D, int H, int W, void *stream);
 
+/* The margins of every pixel's cost curve (no reference counterpart): one streaming scan of a (D,H,W) volume -- what left.bin / right.bin
+ * hold -- that keeps, beside the arg-min, the runner-up and the runner-up among the curve's local minima.  For the curve c[0..D) of a pixel,
+ * with the plain fp32 comparisons (a NaN never wins a `<` and never blocks a negated one; values are finite, NaN or +INF):
+ *   d1   the first strict minimum from +INF, bit for bit what mc_argmin writes (0 for a curve with no value below +INF);
+ *   c1   c[d1], or +INF where no value is below +INF;
+ *   c2   the smallest c[d] over d != d1 with c[d] < +INF (a tie with c1 at a later d gives c2 == c1), +INF where there is none;
+ *   c2l  the smallest c[d] over d != d1 where d is a local minimum: c[d] < +INF, !(c[d-1] <= c[d]) and !(c[d+1] < c[d]), a missing
+ *        neighbour counting as NaN (a plateau counts once, at its first d; d1 always is one), +INF where there is none.
+ * No arithmetic touches a cost: every output is an index, +INF or one of the volume's own bit patterns.  Each output is an optional (H,W)
+ * map; at least one must be given, and none may overlap the volume or another.  Runs in mc_argmin's kernels, which take their four-pixel
+ * form where H*W and every base given are multiples of 16 bytes. */
+int mc_cost_margins(const float *vol, int D, int H, int W, float *d1_out, float *c1_out, float *c2_out, float *c2l_out, void *stream);
+
 /* adcensus.outlier_detection(d0, d1, outlier, disp_max), adcensus.cu:901-918 (kernel 878-899). */
 int mc_outlier_detection(const float *d0, const float *d1, float *outlier, int H, int W,
                          int disp_max, void *stream);

@@ -16,7 +16,7 @@ SYMBOLS = [
     "mc_version", "mc_last_error", "mc_fill_nan", "mc_stereo_join", "mc_ad", "mc_census_scratch_bytes", "mc_census_ws", "mc_fc_stack_workspace_bytes", "mc_fc_stack", "mc_conv3x3_workspace_bytes", "mc_conv3x3",
     "mc_fix_border",
     "mc_cross", "mc_cbca", "mc_cbca_scratch_bytes", "mc_cbca_ws", "mc_sgm2_tmp_bytes", "mc_sgm2", "mc_dhw_to_hwd", "mc_hwd_to_dhw", "mc_scale",
-    "mc_argmin", "mc_spatial_argmin", "mc_outlier_detection", "mc_interpolate_occlusion",
+    "mc_argmin", "mc_spatial_argmin", "mc_cost_margins", "mc_outlier_detection", "mc_interpolate_occlusion",
     "mc_interpolate_mismatch", "mc_subpixel_enchancement", "mc_median2d", "mc_mean2d", "mc_gaussian_host",
     "mc_normalize_forward", "mc_predict_workspace_bytes", "mc_predict_workspace_bytes_full", "mc_predict", "mc_predict_ex", "mc_predict_views", "mc_predict_timed",
     "mc_cbca_plan_bytes", "mc_cbca_ws_cfg", "mc_transpose_cfg",
@@ -68,6 +68,7 @@ def _load():
         "mc_scale": [vp, vp, i64, f, vp],
         "mc_argmin": [vp, vp, i, i, i, vp],
         "mc_spatial_argmin": [vp, vp, i, i, i, vp],
+        "mc_cost_margins": [vp, i, i, i, vp, vp, vp, vp, vp],
         "mc_outlier_detection": [vp, vp, vp, i, i, i, vp],
         "mc_interpolate_occlusion": [vp, vp, vp, i, i, vp],
         "mc_interpolate_mismatch": [vp, vp, vp, i, i, vp],

@@ -400,6 +400,17 @@ def argmin(vol):
     return out
 
 
+def cost_margins(vol):
+    """mc_cost_margins (no counterpart in libadcensus): one scan of a (D,H,W) volume.  Returns (d1, c1, c2, c2l), (1,1,H,W) each: the arg-min
+    as argmin gives it, the minimum, the smallest cost at another disparity and the smallest local minimum at another disparity (+INF where
+    there is none; include/mc_adcensus.h states the comparisons)."""
+    _chk(vol)
+    D, H, W = vol.shape[-3:]
+    d1, c1, c2, c2l = (torch.empty((1, 1, H, W), dtype=torch.float32, device=vol.device) for _ in range(4))
+    check(lib.mc_cost_margins(_p(vol), D, H, W, _p(d1), _p(c1), _p(c2), _p(c2l), _stream()), "cost_margins")
+    return d1, c1, c2, c2l
+
+
 def gaussian(sigma):
     """gaussian(sigma) -- main.lua:528-540: host doubles, returned as a float32 CPU tensor."""
     import ctypes as C

@@ -328,6 +328,22 @@ int mc_spatial_argmin(const float *vol, float *out, int D, int H, int W, void *s
 	return argmin_dhw(vol, out, D, H, W, 1, as_stream(stream));
 }
 
+int mc_cost_margins(const float *vol, int D, int H, int W, float *d1_out, float *c1_out, float *c2_out, float *c2l_out, void *stream)
+{
+	MC_REQUIRE(dims_ok(D, H, W), "mc_cost_margins: bad dims D=%d H=%d W=%d", D, H, W);
+	MC_REQUIRE(vol, "mc_cost_margins: null volume");
+	MC_REQUIRE(d1_out || c1_out || c2_out || c2l_out, "mc_cost_margins: no output asked for");
+	const size_t map_bytes = (size_t)H * W * sizeof(float);
+	struct Range { const char *name; uintptr_t at; size_t bytes; };
+	const Range r[5] = {{"vol", (uintptr_t)vol, map_bytes * D}, {"d1_out", (uintptr_t)d1_out, map_bytes}, {"c1_out", (uintptr_t)c1_out, map_bytes},
+	                    {"c2_out", (uintptr_t)c2_out, map_bytes}, {"c2l_out", (uintptr_t)c2l_out, map_bytes}};
+	for (int i = 1; i < 5; ++i)
+		for (int j = 0; j < i; ++j)
+			MC_REQUIRE(!r[i].at || !r[j].at || r[i].at + r[i].bytes <= r[j].at || r[j].at + r[j].bytes <= r[i].at,
+			           "mc_cost_margins: %s overlaps %s", r[i].name, r[j].name);
+	return cost_margins_dhw(vol, d1_out, c1_out, c2_out, c2l_out, D, H, W, as_stream(stream));
+}
+
 int mc_outlier_detection(const float *d0, const float *d1, float *outlier, int H, int W, int disp_max, void *stream)
 {
 	MC_REQUIRE(d0 && d1 && outlier, "mc_outlier_detection: null pointer");

@@ -14,6 +14,10 @@ int scale(const float *in, float *out, int64_t n, float s, hipStream_t st);
 int transpose(const float *in, float *out, int64_t R, int64_t Cn, int64_t ldin, int64_t ldout, float s, hipStream_t st, int nt = -1);
 int fix_border(float *vol, int D, int H, int W, int n, int direction, hipStream_t st);
 int argmin_dhw(const float *vol, float *out, int D, int H, int W, int base1, hipStream_t st);
+// mc_cost_margins: argmin_dhw's kernels (base1 = 0) with up to three (H,W) maps of the cost curve beside the arg-min d1 -- its minimum c1, the
+// smallest value at another d (c2) and the smallest local minimum at another d (c2l); any may be null, not all four.  (A name of its own, as
+// subpixel_conf below: the host checks of predict.hip define argmin_dhw as it stands above.)
+int cost_margins_dhw(const float *vol, float *d1, float *c1, float *c2, float *c2l, int D, int H, int W, hipStream_t st);
 int outlier_detection(const float *d0, const float *d1, float *outlier, int H, int W, int disp_max, hipStream_t st);
 // mask: one bit per pixel, set where outlier == 2 (word p >> 5, bit p & 31 of the flat pixel index p; (H*W + 31) / 32 words): written by
 // interpolate_occlusion, read by interpolate_mismatch, which walks its rays on an LDS copy of it where the image has at most 524288 pixels

@@ -177,12 +177,64 @@ int fix_border(float *vol, int D, int H, int W, int n, int direction, hipStream_
 
 // ---- argmin -------------------------------------------------------------------------------
 // torch.min(vol,2)-1 (main.lua:1049-1050) with the spatial_argmin convention (adcensus.cu:244-262).
+
+// mc_cost_margins: what one forward pass keeps of a pixel's cost curve besides the arg-min.  m1 / a1 are the arg-min loop's own pair; m2 is
+// the smallest value at another d (a value that loses its place as m1 moves down, or one that never was m1); l1 / l2 are the same pair over
+// the curve's local minima only -- d is one where c[d] < +INF, !(c[d-1] <= c[d]) and !(c[d+1] < c[d]), a missing neighbour counting as NaN,
+// so a plateau counts once, at its first d.  pv is the previous value and pc says that it passed the first two of these tests; the third is
+// taken when the next value arrives (margin_step) or the curve ends (margin_end).  The arg-min is a local minimum under this rule and no
+// local minimum in front of it has its value, so l1 is c[a1] and l2 the smallest local minimum at another d.  Only comparisons: every
+// value kept is +INF or one of the curve's own bit patterns.
+struct Margin {
+	float m1 = __builtin_inff(), m2 = __builtin_inff(), l1 = __builtin_inff(), l2 = __builtin_inff(), pv = __builtin_nanf("");
+	int a1 = 0;
+	bool pc = false;
+};
+static __device__ __forceinline__ void margin_local_min(Margin &s)
+{
+	if (s.pv < s.l1) {
+		s.l2 = s.l1;
+		s.l1 = s.pv;
+	} else if (s.pv < s.l2) {
+		s.l2 = s.pv;
+	}
+}
+static __device__ __forceinline__ void margin_step(Margin &s, float val, int i)
+{
+	if (s.pc && !(val < s.pv)) margin_local_min(s);
+	s.pc = val < __builtin_inff() && !(s.pv <= val);
+	s.pv = val;
+	if (val < s.m1) {
+		s.m2 = s.m1;
+		s.m1 = val;
+		s.a1 = i;
+	} else if (val < s.m2) {
+		s.m2 = val;
+	}
+}
+static __device__ __forceinline__ void margin_end(Margin &s)
+{
+	if (s.pc) margin_local_min(s);
+}
+
 // (D,H,W): one thread per pixel, coalesced along x.  base1 = 1 gives spatial_argmin's 1-based output.
+// c1 / c2 / c2l (uniform over the grid: one scalar branch in front of the loop): all three null is the arg-min alone; with one of them the
+// loop keeps a Margin per pixel and every output, out included, is optional.
 __global__ void __launch_bounds__(256) argmin_dhw_kernel(const float *__restrict__ vol, float *__restrict__ out, int D, int64_t HW,
-                                                         int base1)
+                                                         int base1, float *__restrict__ c1, float *__restrict__ c2, float *__restrict__ c2l)
 {
 	const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (p >= HW) return;
+	if (c1 || c2 || c2l) {
+		Margin s;
+		for (int i = 0; i < D; ++i) margin_step(s, __builtin_nontemporal_load(vol + i * HW + p), i);
+		margin_end(s);
+		if (out) out[p] = (float)(s.a1 + base1);
+		if (c1) c1[p] = s.m1;
+		if (c2) c2[p] = s.m2;
+		if (c2l) c2l[p] = s.l2;
+		return;
+	}
 	int argmin = 0;
 	float mn = __builtin_inff();
 	for (int i = 0; i < D; ++i) {
@@ -197,10 +249,26 @@ __global__ void __launch_bounds__(256) argmin_dhw_kernel(const float *__restrict
 
 // ... four pixels per thread (16-byte loads) where the plane stride and the bases allow
 __global__ void __launch_bounds__(256) argmin_dhw4_kernel(const float *__restrict__ vol, float *__restrict__ out, int D, int64_t HW,
-                                                          int base1)
+                                                          int base1, float *__restrict__ c1, float *__restrict__ c2, float *__restrict__ c2l)
 {
 	const int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
 	if (p >= HW) return;
+	if (c1 || c2 || c2l) {
+		Margin s0, s1, s2, s3;
+		for (int i = 0; i < D; ++i) {
+			const post_f4 v = __builtin_nontemporal_load((const post_f4 *)(vol + i * HW + p));
+			margin_step(s0, v.x, i);
+			margin_step(s1, v.y, i);
+			margin_step(s2, v.z, i);
+			margin_step(s3, v.w, i);
+		}
+		margin_end(s0); margin_end(s1); margin_end(s2); margin_end(s3);
+		if (out) *(post_f4 *)(out + p) = post_f4{(float)(s0.a1 + base1), (float)(s1.a1 + base1), (float)(s2.a1 + base1), (float)(s3.a1 + base1)};
+		if (c1) *(post_f4 *)(c1 + p) = post_f4{s0.m1, s1.m1, s2.m1, s3.m1};
+		if (c2) *(post_f4 *)(c2 + p) = post_f4{s0.m2, s1.m2, s2.m2, s3.m2};
+		if (c2l) *(post_f4 *)(c2l + p) = post_f4{s0.l2, s1.l2, s2.l2, s3.l2};
+		return;
+	}
 	int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
 	float m0 = __builtin_inff(), m1 = m0, m2 = m0, m3 = m0;
 	for (int i = 0; i < D; ++i) {
@@ -213,14 +281,28 @@ __global__ void __launch_bounds__(256) argmin_dhw4_kernel(const float *__restric
 	*(post_f4 *)(out + p) = post_f4{(float)(a0 + base1), (float)(a1 + base1), (float)(a2 + base1), (float)(a3 + base1)};
 }
 
-int argmin_dhw(const float *vol, float *out, int D, int H, int W, int base1, hipStream_t st)
+// the four-pixel kernel where H*W and every base that is given are multiples of 16 bytes
+static int argmin_launch(const float *vol, float *out, int D, int H, int W, int base1, float *c1, float *c2, float *c2l, hipStream_t st)
 {
 	const int64_t HW = (int64_t)H * W;
-	if (HW % 4 == 0 && (uintptr_t)vol % 16 == 0 && (uintptr_t)out % 16 == 0)
-		hipLaunchKernelGGL(argmin_dhw4_kernel, dim3(cdiv(HW / 4, 256)), dim3(256), 0, st, vol, out, D, HW, base1);
+	const uintptr_t bases = (uintptr_t)vol | (uintptr_t)out | (uintptr_t)c1 | (uintptr_t)c2 | (uintptr_t)c2l;
+	if (HW % 4 == 0 && bases % 16 == 0)
+		hipLaunchKernelGGL(argmin_dhw4_kernel, dim3(cdiv(HW / 4, 256)), dim3(256), 0, st, vol, out, D, HW, base1, c1, c2, c2l);
 	else
-		hipLaunchKernelGGL(argmin_dhw_kernel, dim3(cdiv(HW, 256)), dim3(256), 0, st, vol, out, D, HW, base1);
+		hipLaunchKernelGGL(argmin_dhw_kernel, dim3(cdiv(HW, 256)), dim3(256), 0, st, vol, out, D, HW, base1, c1, c2, c2l);
 	return check_launch("argmin_dhw");
+}
+
+int argmin_dhw(const float *vol, float *out, int D, int H, int W, int base1, hipStream_t st)
+{
+	return argmin_launch(vol, out, D, H, W, base1, nullptr, nullptr, nullptr, st);
+}
+
+// mc_cost_margins: argmin_dhw's launch with the cost maps.  Any of the four may be null, not all (api.hip): with the three cost maps null
+// the kernels run the arg-min loop, which writes d1.
+int cost_margins_dhw(const float *vol, float *d1, float *c1, float *c2, float *c2l, int D, int H, int W, hipStream_t st)
+{
+	return argmin_launch(vol, d1, D, H, W, 0, c1, c2, c2l, st);
 }
 
 // ---- outlier_detection, adcensus.cu:878-899 ------------------------------------------------

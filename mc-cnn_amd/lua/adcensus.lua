@@ -45,6 +45,7 @@ int mc_sgm2(const float *x0, const float *x1, const float *in_hwd, float *out_hw
             int direction, void *stream);
 int mc_sgm2_contract_violations(const float *in_hwd, int H, int W, int D, unsigned *count, void *stream);
 int mc_spatial_argmin(const float *vol, float *out, int D, int H, int W, void *stream);
+int mc_cost_margins(const float *vol, int D, int H, int W, float *d1_out, float *c1_out, float *c2_out, float *c2l_out, void *stream);
 int mc_outlier_detection(const float *d0, const float *d1, float *outlier, int H, int W, int disp_max, void *stream);
 int mc_interpolate_occlusion(const float *d0, const float *outlier, float *out, int H, int W, void *stream);
 int mc_interpolate_mismatch(const float *d0, const float *outlier, float *out, int H, int W, void *stream);
@@ -207,6 +208,15 @@ function adcensus.spatial_argmin(input, output)              -- adcensus.cu:264-
                                input:size(2), input:size(3), input:size(4), nil), 'spatial_argmin')
 end
 
+-- NEW entry (no counterpart in libadcensus): the margins of every pixel's cost curve in a (1,D,H,W) volume, one scan (mc_cost_margins).
+--   d1, c1, c2, c2l  CudaTensors or nil, at least one: each is resized to (1,1,H,W) and filled -- the arg-min (0-based, as `-a predict`'s
+--   maps), the minimum, the smallest cost at another disparity and the smallest local minimum at another disparity (+INF where none).
+function adcensus.cost_margins(vol, d1, c1, c2, c2l)
+   local D, H, W = vol:size(2), vol:size(3), vol:size(4)
+   local function out(t) return t ~= nil and ptr(t:resize(1, 1, H, W), 'cost_margins') or nil end
+   check(lib.mc_cost_margins(ptr(vol, 'cost_margins'), D, H, W, out(d1), out(c1), out(c2), out(c2l), nil), 'cost_margins')
+end
+
 function adcensus.outlier_detection(d0, d1, outlier, disp_max)   -- adcensus.cu:901-918
    check(lib.mc_outlier_detection(ptr(d0, 'outlier_detection'), ptr(d1, 'outlier_detection'),
                                   ptr(outlier, 'outlier_detection'), d0:size(3), d0:size(4), disp_max, nil),
@@ -307,6 +317,8 @@ end
 --            Two more keys, disp_right= and outlier_right=, ask for the RIGHT view's finished map and classes (mc_predict_views): the
 --            post-processing on the x-mirrored arg-min maps and right volume, mirrored back, for the price of that tail alone; both
 --            volumes are then computed whatever `both` says.
+--            Three more keys, c1=, c2= and c2l=, ask for the margins of the final LEFT volume's cost curves (adcensus.cost_margins above,
+--            which scans the volume this call exports: one is allocated for the scan where `both` is false).
 -- Returns disp (1,1,H,W) and, when `both`, volL, volR (1,disp_max,H,W).
 local SM_TERMINATE = {[''] = 0, cnn = 1, cbca1 = 2, sgm = 3, cbca2 = 4, occlusion = 5, mismatch = 6,
                       subpixel_enchancement = 7, median = 8, bilateral = 9}
@@ -337,6 +349,12 @@ function adcensus.predict(o, dataset, arch, x_batch, input, disp_max, border_n, 
       volL, volR = torch.CudaTensor(1, disp_max, H, W), torch.CudaTensor(1, disp_max, H, W)
       pl, pr = volL:data(), volR:data()
    end
+   local margins = extras ~= nil and (extras.c1 ~= nil or extras.c2 ~= nil or extras.c2l ~= nil)
+   local scanned = volL
+   if margins and scanned == nil then
+      scanned = torch.CudaTensor(1, disp_max, H, W)
+      pl = scanned:data()
+   end
    local x0, x1 = x_batch[1]:data(), x_batch[2]:data()
    ptr(x_batch, 'predict'); ptr(input, 'predict')
    local fl, fr, rl, rr = nil, nil, nil, nil
@@ -356,17 +374,24 @@ function adcensus.predict(o, dataset, arch, x_batch, input, disp_max, border_n, 
       end
    end
    for k in pairs(extras) do
-      if k ~= 'outlier' and k ~= 'cost' and k ~= 'curvature' and k ~= 'disp_right' and k ~= 'outlier_right' then
+      if k ~= 'outlier' and k ~= 'cost' and k ~= 'curvature' and k ~= 'disp_right' and k ~= 'outlier_right' and k ~= 'c1' and k ~= 'c2'
+         and k ~= 'c2l' then
          error('predict: unknown extra ' .. tostring(k), 2)
+      end
+   end
+   for _, k in ipairs({'c1', 'c2', 'c2l'}) do
+      if extras[k] ~= nil and torch.typename(extras[k]) ~= 'torch.CudaTensor' then
+         error(('predict: extras.%s: torch.CudaTensor expected, got %s'):format(k, torch.typename(extras[k]) or type(extras[k])), 2)
       end
    end
    if ex.disp_right ~= nil or ex.outlier_right ~= nil then
       check(lib.mc_predict_views(p, x0, x1, fl, fr, C, rl, rr, disp_max, H, W, ws, need, pl, pr, nil, nil, ex.outlier, ex.cost, ex.curvature,
                                  ex.disp_right, ex.outlier_right, disp:data(), nil), 'predict')
-      return disp, volL, volR
+   else
+      check(lib.mc_predict_ex(p, x0, x1, fl, fr, C, rl, rr, disp_max, H, W, ws, need, pl, pr, nil, nil, ex.outlier, ex.cost, ex.curvature,
+                              disp:data(), nil), 'predict')
    end
-   check(lib.mc_predict_ex(p, x0, x1, fl, fr, C, rl, rr, disp_max, H, W, ws, need, pl, pr, nil, nil, ex.outlier, ex.cost, ex.curvature,
-                           disp:data(), nil), 'predict')
+   if margins then adcensus.cost_margins(scanned, nil, extras.c1, extras.c2, extras.c2l) end
    return disp, volL, volR
 end
 

@@ -11,7 +11,10 @@ with the reference's messages.  `-a time` is main.lua:1140-1167 (min of N runs o
 writes `outlier.bin`, `cost.bin` and `curvature.bin` (1,1,H,W) next to `disp.bin`: the LR check's class of every pixel (0 match, 1 occlusion,
 2 mismatch) and the two confidence measures of the sub-pixel stage (`mc_predict_ex`; no counterpart in main.lua).  `-a predict -right_view`
 also writes `disp_right.bin` (1,1,H,W), the RIGHT view's finished disparity map -- the post-processing on the x-mirrored arg-min maps and
-right volume, mirrored back (`mc_predict_views`) -- and, with `-extras`, its classes as `outlier_right.bin`.
+right volume, mirrored back (`mc_predict_views`) -- and, with `-extras`, its classes as `outlier_right.bin`.  `-a predict -margins` also
+writes `c1.bin`, `c2.bin` and `c2l.bin` (1,1,H,W), the margins of every pixel's cost curve in the final left volume (`mc_cost_margins`: its
+minimum, the runner-up and the runner-up among its local minima), and with `-right_view` `c1_right.bin`, `c2_right.bin` and `c2l_right.bin`
+from the final right volume.
 
 Architectures: fast, slow (feature net + `mc_fc_stack`, main.lua:958-983; `-fc_mode bf16x3` takes the FC stack's products as three
 bf16 products each, `mc_fc_split_stack` of libmcfcsplit.so, wherever arch slow predicts; the default `-fc_mode fp32` is `mc_fc_stack`;
@@ -104,6 +107,9 @@ def parse(argv):
     ap.add_argument("-extras", action="store_true", help="-a predict: also write outlier.bin, cost.bin and curvature.bin (mc_predict_ex)")
     ap.add_argument("-right_view", action="store_true",
                     help="-a predict: also write disp_right.bin, the right view's finished disparity map (mc_predict_views); with -extras also outlier_right.bin")
+    ap.add_argument("-margins", action="store_true",
+                    help="-a predict: also write c1.bin, c2.bin and c2l.bin, the margins of the final left volume's cost curves (mc_cost_margins); "
+                         "with -right_view also c1_right.bin, c2_right.bin and c2l_right.bin")
     add_fc_mode_flag(ap)
     add_conv_mode_flag(ap)
     ap.add_argument("-data_dir", default="", help="default data.kitti / data.kitti2015 (main.lua:427-445)")
@@ -128,6 +134,8 @@ def parse(argv):
         raise SystemExit("main.py: -extras writes outlier.bin, cost.bin and curvature.bin next to disp.bin and goes with -a predict only")
     if opt.right_view and opt.a != "predict":
         raise SystemExit("main.py: -right_view writes disp_right.bin next to disp.bin and goes with -a predict only")
+    if opt.margins and opt.a != "predict":
+        raise SystemExit("main.py: -margins writes c1.bin, c2.bin and c2l.bin next to disp.bin and goes with -a predict only")
     if getattr(opt, "at", 0) == 1 and opt.data_dir:
         raise SystemExit("main.py: -at 1 reads data.kitti and data.kitti2015 together (main.lua:403-426) and takes no -data_dir")
     return dataset, arch, opt, pipeline_prm(t, opt)
@@ -295,10 +303,12 @@ def main(argv=None):
     prm["border_n"] = len(layers)  # (1 + l1*(3-1) - 1) / 2, main.lua:382-391,923
     conv_mode = getattr(opt, "conv_mode", "fp32")   # the feature net's convolutions wherever this command line predicts
 
-    def run(x_batch, D, workspace=None, want_volumes=False, extras=False, right_view=False):
+    def run(x_batch, D, workspace=None, want_volumes=False, extras=False, right_view=False, margins=False):
         more = dict(want_outlier=True, want_confidence=True) if extras else {}   # -extras: mc_predict_ex's three maps
         if right_view:                                                          # -right_view: mc_predict_views' two
             more["want_right"] = True
+        if margins:                                                             # -margins: mc_cost_margins' three, per view
+            more["want_margins"] = True
         if not learned:  # main.lua:932-942: hand-crafted costs straight from the image pair, no border fix
             from . import adcensus
             cost = adcensus.ad if arch == "ad" else adcensus.census
@@ -353,7 +363,7 @@ def main(argv=None):
         x0, x1 = rgb2y(x0), rgb2y(x1)
     D = opt.disp_max
     x_batch = torch.from_numpy(np.stack([normalize(x0), normalize(x1)])).to(dev)  # (2,1,H,W)
-    res = run(x_batch, D, want_volumes=True, extras=opt.extras, right_view=opt.right_view)
+    res = run(x_batch, D, want_volumes=True, extras=opt.extras, right_view=opt.right_view, margins=opt.margins)
     torch.cuda.synchronize()
     H, W = x_batch.shape[2:]
     for name, key in (("right", "volR"), ("left", "volL")):  # main.lua:954-955 writes right.bin first
@@ -367,6 +377,10 @@ def main(argv=None):
             write_bin("%s.bin" % name, res[key].cpu().numpy())
     if opt.right_view:
         for name in ("disp_right",) + (("outlier_right",) if opt.extras else ()):
+            print("Writing %s.bin, %d x %d x %d x %d" % (name, 1, 1, H, W))
+            write_bin("%s.bin" % name, res[name].cpu().numpy())
+    if opt.margins:
+        for name in ("c1", "c2", "c2l") + (("c1_right", "c2_right", "c2l_right") if opt.right_view else ()):
             print("Writing %s.bin, %d x %d x %d x %d" % (name, 1, 1, H, W))
             write_bin("%s.bin" % name, res[name].cpu().numpy())
     return 0

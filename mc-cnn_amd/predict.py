@@ -40,8 +40,10 @@ def stereo_predict(x_batch, params, disp_max, feat=None, raw=None, return_all=Fa
     intermediate maps and the three per-pixel maps of mc_predict_ex: `outlier`
     (the LR check's classes; without the LR check it runs for the map alone),
     `cost` and `curvature` (the left volume around the disparity the sub-pixel
-    stage reads), each (1,1,H,W), and the two maps of mc_predict_views,
-    `disp_right` and `outlier_right` (right_view below)."""
+    stage reads), each (1,1,H,W), the two maps of mc_predict_views,
+    `disp_right` and `outlier_right` (right_view below), and the margins of
+    both final volumes' cost curves, `c1`, `c2`, `c2l` and `c1_right`,
+    `c2_right`, `c2l_right` (cost_margins below: mc_cost_margins with torch alone)."""
     p = make_params(params)
     x0, x1, H, W = _img2(x_batch)
     D = int(disp_max)
@@ -103,9 +105,41 @@ def stereo_predict(x_batch, params, disp_max, feat=None, raw=None, return_all=Fa
     d = adcensus.mean2d(d, adcensus.gaussian(p.blur_sigma).to(dev), p.blur_t)
     if return_all:
         disp_right, outlier_right = right_view(p, disp[2], disp[1], out_vols[1], D)
-        return dict(disp=d, volL=out_vols[-1], volR=out_vols[1], dispL0=disp[2], dispR0=disp[1], outlier=outlier, cost=cost,
-                    curvature=curvature, disp_right=disp_right, outlier_right=outlier_right)
+        res = dict(disp=d, volL=out_vols[-1], volR=out_vols[1], dispL0=disp[2], dispR0=disp[1], outlier=outlier, cost=cost,
+                   curvature=curvature, disp_right=disp_right, outlier_right=outlier_right)
+        for direction, suffix in ((-1, ""), (1, "_right")):
+            _, res["c1" + suffix], res["c2" + suffix], res["c2l" + suffix] = cost_margins(out_vols[direction])
+        return res
     return d
+
+
+def _first_min(vals):
+    """(index, value) of the first minimum along dim 1 of a (1,D,H,W) tensor without NaN: the value is gathered, so it keeps its bits"""
+    D = vals.shape[1]
+    idx = torch.arange(D, device=vals.device).reshape(1, D, 1, 1)
+    m = vals.min(dim=1, keepdim=True).values
+    at = torch.where(vals == m, idx, D).min(dim=1, keepdim=True).values
+    return at, vals.gather(1, at)
+
+
+def cost_margins(vol):
+    """mc_cost_margins with torch alone, for a (1,D,H,W) volume: (d1, c1, c2, c2l), (1,1,H,W) each.  Values that are not below +INF
+    (NaN, +INF) are no candidates; d1 is the first minimum of the rest (0 where there is none) and c1 its cost; c2 is the smallest
+    candidate at another d; c2l is the smallest at another d among the local minima -- candidates with !(c[d-1] <= c[d]) and
+    !(c[d+1] < c[d]), the comparisons taken on shifted copies whose missing neighbour is NaN.  +INF where there is none."""
+    D = vol.shape[1]
+    inf = torch.full_like(vol, float("inf"))
+    idx = torch.arange(D, device=vol.device).reshape(1, D, 1, 1)
+    valid = vol < inf
+    d1, c1 = _first_min(torch.where(valid, vol, inf))
+    d1 = torch.where(c1 < inf[:, :1], d1, torch.zeros_like(d1))
+    others = valid & (idx != d1)
+    _, c2 = _first_min(torch.where(others, vol, inf))
+    nan = torch.full_like(vol[:, :1], float("nan"))
+    before, after = torch.cat([nan, vol[:, :-1]], 1), torch.cat([vol[:, 1:], nan], 1)
+    local_min = others & ~(before <= vol) & ~(after < vol)
+    _, c2l = _first_min(torch.where(local_min, vol, inf))
+    return d1.to(torch.float32), c1, c2, c2l
 
 
 def right_view(p, dispL0, dispR0, volR, D):
@@ -165,7 +199,8 @@ class Workspace:
 
 
 def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspace=None, want_volumes=False,
-                         want_disp0=False, out=None, timed=False, want_outlier=False, want_confidence=False, want_right=False):
+                         want_disp0=False, out=None, timed=False, want_outlier=False, want_confidence=False, want_right=False,
+                         want_margins=False):
     """The whole of stereo_predict from the cost-volume stage on, in one C-ABI call.
 
     want_outlier adds res["outlier"], the LR check's class per pixel (0 match, 1 occlusion, 2 mismatch); want_confidence adds
@@ -173,7 +208,12 @@ def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspa
     curve there.  Each is (1,1,H,W); with either flag the call is mc_predict_ex, otherwise mc_predict.
 
     want_right adds res["disp_right"] and res["outlier_right"], the right view's finished disparity map and its classes (right_view
-    above states them op by op); the call is then mc_predict_views, and the right view costs the (H,W) tail alone."""
+    above states them op by op); the call is then mc_predict_views, and the right view costs the (H,W) tail alone.
+
+    want_margins adds res["c1"], res["c2"] and res["c2l"], the margins of every pixel's cost curve in the final left volume
+    (mc_cost_margins: the minimum, the smallest cost at another disparity, the smallest local minimum at another disparity), and with
+    want_right also res["c1_right"], res["c2_right"], res["c2l_right"] from the final right volume.  The volumes are exported for the
+    scan, which follows the pipeline's call on the same stream; they are returned with want_volumes only."""
     p = make_params(params)
     x0, x1, H, W = _img2(x_batch)
     D = int(disp_max)
@@ -202,10 +242,17 @@ def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspa
         res["stage_ms"] = dict(zip(STAGES, list(ms)))
         return res
     vl = vr = dl = dr = None
+    scan = {}   # want_margins: suffix of the three keys -> the exported volume they are scanned from
     if want_volumes:
         res["volL"] = torch.empty((1, D, H, W), dtype=torch.float32, device=dev)
         res["volR"] = torch.empty((1, D, H, W), dtype=torch.float32, device=dev)
         vl, vr = res["volL"].data_ptr(), res["volR"].data_ptr()
+    if want_margins:
+        scan[""] = res["volL"] if want_volumes else torch.empty((1, D, H, W), dtype=torch.float32, device=dev)
+        vl = scan[""].data_ptr()
+        if want_right:
+            scan["_right"] = res["volR"] if want_volumes else torch.empty((1, D, H, W), dtype=torch.float32, device=dev)
+            vr = scan["_right"].data_ptr()
     if want_disp0:
         res["dispL0"] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
         res["dispR0"] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
@@ -227,5 +274,10 @@ def stereo_predict_fused(x_batch, params, disp_max, feat=None, raw=None, workspa
     else:
         check(lib.mc_predict(C.byref(p), x0.data_ptr(), x1.data_ptr(), fl, fr, Cn, rl, rr, D, H, W, workspace.ptr,
                              ws_bytes, vl, vr, dl, dr, out.data_ptr(), st), "mc_predict")
+    for suffix, vol in scan.items():
+        for name in ("c1", "c2", "c2l"):
+            res[name + suffix] = torch.empty((1, 1, H, W), dtype=torch.float32, device=dev)
+        check(lib.mc_cost_margins(vol.data_ptr(), D, H, W, None, res["c1" + suffix].data_ptr(), res["c2" + suffix].data_ptr(),
+                                  res["c2l" + suffix].data_ptr(), st), "mc_cost_margins")
     del keep
     return res
